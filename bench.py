@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- the metric BASELINE.json names: Mpixels/s on the Ghostscript Tiger at
-3840x2160 (fills + strokes, BASELINE config 3) on 1/2/4/8 GPUs, with the HBM-roofline
-fraction of the dominant kernel and the CPU oracle timed beside it.
+3840x2160 (fills + strokes, BASELINE config 3) on 1/2/4/8 GPUs; with --full also the
+HBM-roofline fraction of the dominant kernel and the CPU oracle timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and measures `value` (below); --dump-outputs DIR
+also writes the frame of the last timed step (bench.dump_outputs).  Everything else -- the same
+step host-timed, per-kernel durations and the roofline, the RCCL binding, the config 5 block and
+the CPU baseline -- is measured with --full only.
 
 A "step" is one frame of the hot path -- pm_bin_kernel, then pm_fine_kernel (list building fused in)
 (tileKernel + renderKernel + composite of the reference) -- over the scene already
@@ -25,12 +30,12 @@ frame -- rank r renders a band of tile rows (cost-balanced cuts from measured ba
 and every step ends with the one collective of the design: the bands are gathered straight
 into the final image on rank 0 (one grouped send/recv over RCCL/xGMI).  value is then
 W*H / t_frame with t_frame = one step alone (band render + gather) between two events on the
-frame's stream -- the GPU's clock, as at N = 1 --, MAX over ranks; the same step host-timed
-(t_frame_e2e), t_render (slowest rank's band), t_gather and the sustained end-to-end rate are
-reported next to it; config.rccl_lib / rccl_ranks name the RCCL the product's collective is
-bound to.  A "config5" block carries the same measurements for BASELINE config 5 (8192^2 grid
-of 25 Tigers), where the frame is big enough to shard; `--workload config5` makes it the main
-line (also with --gpus N).
+frame's stream -- the GPU's clock, as at N = 1 --, MAX over ranks; the sustained end-to-end
+rate is reported next to it, and with --full the same step host-timed (t_frame_e2e), t_render
+(slowest rank's band) and t_gather; config.rccl_lib / rccl_ranks name the RCCL the product's
+collective is bound to.  With --full a "config5" block carries the same measurements for
+BASELINE config 5 (8192^2 grid of 25 Tigers), where the frame is big enough to shard;
+`--workload config5` makes it the main line (also with --gpus N).
 """
 from __future__ import annotations
 
@@ -380,11 +385,16 @@ def main() -> int:
     ap.add_argument("--gather-chunks", type=int, default=1,
                     help="N>1: every rank renders its band in this many sub-bands (a context each) and posts each sub-band's gather on a "
                          "second stream while it renders the next: the exchange runs under the render instead of behind it")
-    ap.add_argument("--no-config5", action="store_true", help="skip the BASELINE config 5 block")
+    ap.add_argument("--no-config5", action="store_true", help="--full: skip the BASELINE config 5 block")
     ap.add_argument("--workload", choices=["config2", "config3", "config4", "config5", "held1", "held2", "held3"], default="config3",
                     help="the main line's workload (default: BASELINE config 3, the one the metric is quoted on; the others are for profiles/)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--dump", default=None, help="rank 0 saves the last gathered frame as .npy (tests)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes the frame of the last timed step to DIR/frame.npy: a fixed, seeded sample of its pixels as float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: lone frames host-timed, per-kernel durations and the roofline, "
+                         "the RCCL binding, the config 5 block and the CPU baseline")
     args = ap.parse_args()
 
     import torch
@@ -421,10 +431,10 @@ def main() -> int:
             args.gather_impl = "sendrecv"  # (the rehearsal's ranks share one GPU: no RCCL communicator between them)
 
     r = pm.Renderer(local)
-    held = pm.workloads.heldout_workloads()
     wl = {"config2": lambda: pm.workloads.tiger(1920, 1080, fills_only=True), "config3": lambda: pm.workloads.tiger(3840, 2160),
           "config4": pm.workloads.config4_blobs, "config5": pm.workloads.config5_tiger_grid,
-          "held1": lambda: held["held1"], "held2": lambda: held["held2"], "held3": lambda: held["held3"]}[args.workload]()
+          "held1": lambda: pm.workloads.heldout_workloads()["held1"], "held2": lambda: pm.workloads.heldout_workloads()["held2"],
+          "held3": lambda: pm.workloads.heldout_workloads()["held3"]}[args.workload]()
     workload_name = {"config2": "BASELINE config 2: Ghostscript Tiger 1920x1080, solid fills only",
                      "config3": "BASELINE config 3: Ghostscript Tiger 3840x2160, fills + strokes",
                      "config4": "BASELINE config 4: 10k overlapping cubic-Bezier paths, 4096x4096",
@@ -443,17 +453,20 @@ def main() -> int:
     elapsed = job.sustained(args.steps, args.warmup, precondition)
     ms_per_step = elapsed / args.steps * 1e3
     sustained = px / (elapsed / args.steps) / 1e6
+    frame = last_frame(job, r) if args.dump_outputs and rank == 0 else None  # (what the last timed step computed)
 
     n_lat = max(100, min(args.steps, 400))
-    t_frame_host = job.lone_frame_host_ms(min(n_lat, 100))
+    if args.full:
+        t_frame_host = job.lone_frame_host_ms(min(n_lat, 100))
     if world == 1:
         lat = r.frame_latency(n_lat)
         t_frame = lat["median_ms"]
         t_render, t_gather = t_frame, 0.0
-        tm = r.time_frames(max(10, min(args.steps, 2000)), pipelined=True)
-        alone = r.time_frames(20)
-        n_overlapped, n_serial = precondition + args.warmup + args.steps + tm["iters"], alone["iters"] + lat["iters"] + min(n_lat, 100) + 1
-    else:
+        if args.full:
+            tm = r.time_frames(max(10, min(args.steps, 2000)), pipelined=True)
+            alone = r.time_frames(20)
+            n_overlapped, n_serial = precondition + args.warmup + args.steps + tm["iters"], alone["iters"] + lat["iters"] + min(n_lat, 100) + 1
+    elif args.full:
         # band render alone (kernel timestamps), slowest rank; the gather alone; one whole step alone
         job.r.render_to(job.band, job.stream)
         job.fence()
@@ -464,150 +477,26 @@ def main() -> int:
         tm = r.time_frames(max(10, min(args.steps, 500)), pipelined=True)
         alone = r.time_frames(20)
         n_overlapped = n_serial = 1
+    else:
+        t_frame = job.lone_frame_event_ms(min(n_lat, 100))
     st = r.stats()
     value = px / (t_frame * 1e-3) / 1e6
-    rccl = job.rccl_info()
+    if args.full:
+        rccl = job.rccl_info()
 
+    run_config5 = args.full and not args.no_config5
     cfg5 = None
-    if not args.no_config5:
+    if run_config5:
         cfg5 = config5_block(pm, pmd, torch, dist, r, rank, world, local, args)
 
     if rank == 0:
-        rows = job.layout[rank][2]
-        b_alg = job.scene_bytes + 4 * W * rows  # this rank's launch: scene read once + its pixels written once
-        b_alg_frame = world * job.scene_bytes + 4 * px
-        kernels = {"pm_bin_kernel": tm["bin_ms"], "pm_coarse_kernel": tm["coarse_ms"], "pm_fine_kernel": tm["fine_ms"], "pm_clear_kernel": tm["clear_ms"]}
-        alone_ms = {"pm_bin_kernel": alone["bin_ms"], "pm_coarse_kernel": alone["coarse_ms"], "pm_fine_kernel": alone["fine_ms"], "pm_clear_kernel": alone["clear_ms"]}
-        if kernels["pm_clear_kernel"] == 0:  # folded into pm_fine_kernel's launch
-            kernels.pop("pm_clear_kernel")
-        if alone_ms["pm_clear_kernel"] == 0:  # (a frame alone folds it by default, frames behind others do not)
-            alone_ms.pop("pm_clear_kernel")
-        if kernels["pm_coarse_kernel"] == 0:  # fused: pm_fine_kernel<true> builds each tile's list itself
-            kernels.pop("pm_coarse_kernel")
-            alone_ms.pop("pm_coarse_kernel")
-        # the dominant kernel and its duration: kernels serialized on one stream, every launch alone on the
-        # GPU (a duration that fits inside a step; with four frames in flight the launches stretch each
-        # other and their in-flight durations exceed ms_per_step: kept below as *_inflight)
-        dom = max(alone_ms, key=alone_ms.get)
-        dom_ms = alone_ms[dom]
-        achieved = b_alg / (dom_ms * 1e-3) / 1e9
-        dom_inflight_ms = kernels[dom]
-        pipelined_ms = tm["total_ms"] / tm["iters"]
-        traffic, traffic_frame, issue, traffic_meta = None, None, None, None
-        # (one committed PMC digest per workload: the Tiger's is hbm_traffic.json, the others' hbm_traffic_<workload>.json)
-        tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json" if args.workload == "config3" else f"hbm_traffic_{args.workload}.json")
-        if os.path.exists(tpath) and world == 1:
-            try:
-                prof = json.load(open(tpath))
-                # the PMC figures are copied from a committed profile, not measured in this run: say which
-                # kernels they were taken on, and whether those are the kernels running now
-                sys.path.insert(0, os.path.join(ROOT, "tools"))
-                from make_traffic import kernel_sources_sha16
-
-                now = kernel_sources_sha16()
-                traffic_meta = {"source": prof.get("_source"), "measured_at_commit": prof.get("_commit"),
-                                "kernel_sources_sha16": prof.get("_kernel_sources_sha16"), "kernel_sources_sha16_now": now,
-                                "stale": prof.get("_kernel_sources_sha16") != now}
-                if traffic_meta["stale"]:
-                    print(f"bench.py: profiles/hbm_traffic.json was measured on other kernel sources ({prof.get('_kernel_sources_sha16')} at commit "
-                          f"{prof.get('_commit')}, now {now}): roofline.traffic / issue_roofline are from that profile", file=sys.stderr)
-                traffic = prof.get(dom, {}).get("hbm_bytes_per_launch")
-                # (the counted runs pin PM_FOLD_CLEAR=1, tools/prof_round.sh: a frame is the launches a frame ALONE
-                #  makes, clearing inside the tile kernel's -- a separate pm_clear_kernel moves the same bytes)
-                counted = [k for k in alone_ms if k != "pm_clear_kernel"]
-                per_kernel = [prof[k]["hbm_bytes_per_launch"] for k in counted if "hbm_bytes_per_launch" in prof.get(k, {})]
-                if len(per_kernel) == len(counted):
-                    traffic_frame = {"hbm_bytes_per_frame": int(sum(per_kernel)), "ratio_to_algorithmic": round(sum(per_kernel) / b_alg, 3)}
-                insts = sum(prof[k]["valu_insts_per_launch"] for k in counted if "valu_insts_per_launch" in prof.get(k, {}))
-                props = torch.cuda.get_device_properties(local)
-                n_simd = props.multi_processor_count * 4
-                clock_ghz = getattr(props, "clock_rate", 2400000) / 1e6
-                if insts:
-                    # CDNA4 SIMDs are 32 lanes wide: a wave64 VALU instruction issues in 2 cycles
-                    # (MI355X_MICROARCH.md, per-instruction constants); counts = SQ_INSTS_VALU of
-                    # the committed PMC passes, one launch of each kernel = one frame
-                    floor_ms = insts * 2 / n_simd / (clock_ghz * 1e9) * 1e3
-                    issue = {"bound": "valu-issue", "valu_wave_insts_per_frame": insts, "simds": n_simd, "cycles_per_inst": 2,
-                             "clock_ghz": round(clock_ghz, 3), "floor_ms": round(floor_ms, 5),
-                             "frac_sustained": round(floor_ms / ms_per_step, 4), "frac_lone_frame": round(floor_ms / t_frame, 4),
-                             "source": prof.get("_source")}
-            except Exception:
-                traffic, traffic_frame, issue = None, None, None
-        out = {
-            "metric": "Mpixels/s, Ghostscript Tiger 3840x2160 (fills+strokes): W*H / t_frame" if args.workload == "config3" else f"Mpixels/s, {workload_name}: W*H / t_frame",
-            "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "t_frame_ms": round(t_frame, 5),
-            "value_definition": ("W*H / t_frame; t_frame = one frame alone, first kernel begin to last kernel end: two HIP events on the frame's stream "
-                                 f"around the plain launches pm_render makes (pm_frame_latency), median of {lat['iters']} (SURVEY.md 8d)") if world == 1 else
-                                ("W*H / t_frame; t_frame = one step alone -- band render + gather into the final image on rank 0 -- between two events on "
-                                 "the frame's stream (the GPU clock of the N=1 figure), median, MAX over ranks; t_frame_host_ms / config.t_frame_e2e_ms is the "
-                                 "same step host-timed incl. launch latency and the device sync"),
-            "sustained_mpix_s": round(sustained, 1), "ms_per_step": round(ms_per_step, 5),
-            "sustained_definition": "W*H / (wall time of the K timed steps / K), steps submitted back to back, barrier + device sync on both sides, MAX over ranks"
-                                    + ("" if world == 1 else "; every step ends with the gather to rank 0"),
-            "t_frame_host_ms": round(t_frame_host, 5),
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-            "dtype": "f32 geometry + f16 accumulators (as the reference)", "data": {"config2": "synthetic: embedded Ghostscript_Tiger.svg, scale 5.4, fills only, flattened on device",
-                                                                                "config3": "synthetic: embedded Ghostscript_Tiger.svg, scale 10.8, flattened on device",
-                                                                                "config4": "synthetic: 10 000 random closed cubic paths (SplitMix64 seed 0x5EED0004), flattened on device",
-                                                                                "config5": "synthetic: 5x5 grid of the embedded Ghostscript_Tiger.svg at scale 8, flattened on device",
-                                                                                "held1": "synthetic: embedded Ghostscript_Tiger.svg, scale 7.2, flattened on device",
-                                                                                "held2": "synthetic: 2 000 random closed cubic paths (SplitMix64 seed 0x5EED0008), flattened on device",
-                                                                                "held3": "synthetic: 20 000 glyph-like closed paths (SplitMix64 seed 0x5EED0007), flattened on device"}[args.workload],
-            "config": {
-                "workload": workload_name,
-                "viewport": [W, H], "items": job.n_items, "scene_bytes": job.scene_bytes,
-                "parallelism": "1 GPU" if world == 1 else f"tile-row bands x{world} ({'near-equal' if args.equal_bands else 'cost-balanced'} cuts), scene replicated, "
-                               f"{ {'cabi': 'pm_gather (C ABI: grouped RCCL send/recv)', 'sendrecv': 'grouped send/recv (torch.distributed)', 'allgather': 'padded all-gather'}.get(job.gather_impl, job.gather_impl) } "
-                               "of the bands into the final image on rank 0 in every step",
-                "gather_impl": None if world == 1 else job.gather_impl,
-                "gather_chunks": None if world == 1 else max(1, len(job.chunks)),
-                "rccl_lib": rccl.get("rccl_lib"), "rccl_ranks": rccl.get("rccl_ranks"), **({"rccl_error": rccl["rccl_error"]} if "rccl_error" in rccl else {}),
-                "band_cuts": job.cuts, "balance": job.balance_log or None,
-                "t_render_ms": round(t_render, 5), "t_gather_ms": round(t_gather, 5), "t_frame_e2e_ms": round(t_frame_host, 5),
-                # (what t_gather cannot beat: the largest non-root band over one xGMI link at ~153 GB/s; launch latency comes on top)
-                "t_gather_wire_floor_ms": None if world == 1 else round(pmd.gather_wire_floor_ms(job.layout, W, world), 5),
-                **({"gather_fallback": job.gather_fallback} if world > 1 and getattr(job, "gather_fallback", "") else {}),
-                "queued_tiles_rank0": st["queued_tiles"], "precondition_steps": precondition,
-            },
-            "scene": {
-                "flatten_encode_ms": round(job.scene_t["flatten_encode_ms"], 4), "scene_index_host_ms": round(job.scene_t["scene_index_ms"], 4),
-                "arena_setup_host_ms": round(job.scene_t["arena_setup_ms"], 4), "first_frame_ms": round(job.first_frame_ms, 4),
-                "first_frame_parts": job.first_frame_parts,
-                "note": "once per scene, like the reference encodes once per resize (PietRenderer.m:145): flatten_encode = pm_flatten_and_encode's four kernels + "
-                        "their read-backs; scene_index = header/item read-back, validation, pm_index_kernel; arena_setup = per-(scene, viewport) sizing on the host, "
-                        "paid by the first frame; first_frame = all of it fused, resize -> first frame complete (host wall clock)",
-            },
-            "roofline": {
-                "bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_frame": traffic_frame, "traffic_profile": traffic_meta,
-                "algorithmic_bytes_per_launch": b_alg, "kernel_ms": round(dom_ms, 5),
-                "kernels_alone_ms": {k: round(v, 5) for k, v in alone_ms.items()},
-                "kernels_inflight_ms": {k: round(v, 5) for k, v in kernels.items()},
-                "frac_inflight": round(b_alg / (dom_inflight_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "frac_serial_frame": round(b_alg / (sum(alone_ms.values()) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "trace_average_ms": {k: round((n_overlapped * kernels[k] + n_serial * alone_ms.get(k, 0.0)) / (n_overlapped + (n_serial if k in alone_ms else 0)), 5) for k in kernels},
-                "trace_average_note": "what the AverageNs column of a kernel trace of THIS command shows: the mix of in-flight and serialized launches it makes",
-                "frame_latency_ms": round(t_render, 5),
-                "frac_frame": round(b_alg_frame / world / (t_render * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "frame_pipelined_ms": round(pipelined_ms, 5),
-                "frac_frame_pipelined": round(b_alg / (pipelined_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                "note": "frac credits the whole frame's bytes to ONE of the frame's kernels; frac_serial_frame = the same bytes / the SUM of the kernels' serialized "
-                        "durations (the frame's kernels back to back, no gaps) and frac_frame = / the lone frame: read those as the path's fraction of HBM peak. "
-                        "achieved/frac: algorithmic bytes of one launch / the dominant kernel's average launch duration with the kernels serialized on one "
-                        "stream, events carried by the dispatches (what a rocprofv3 --kernel-trace of PM_FRAME_STREAMS=1 PM_SLOTS=1 shows: "
-                        "profiles/*_serial_kernel_stats.csv); frac_inflight / kernels_inflight_ms: the same launches inside the overlapping batch of the "
-                        "timed steps (four frames in flight: the durations stretch each other and exceed ms_per_step; what the default kernel trace "
-                        "shows); frac_frame: B_alg(N)/N / the slowest rank's lone-frame time (SURVEY 8d multi-GPU roofline); frac_frame_pipelined: "
-                        "B_alg / ms_per_step; the path is latency bound, not HBM bound (DESIGN.md)",
-            },
-        }
-        if issue is not None:
-            out["issue_roofline"] = issue
-        if cfg5 is not None:
-            out["config5"] = cfg5
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(pm, pm.workloads.tiger(3840, 2160))
+        out = headline(args, job, world, value, t_frame, ms_per_step, sustained, workload_name, st, precondition,
+                       lat["iters"] if world == 1 else None)
+        if args.full:
+            out = full_report(out, args, job, torch, rank, world, local, W, px, t_frame, t_frame_host, t_render, t_gather, ms_per_step,
+                              tm, alone, n_overlapped, n_serial, rccl, cfg5, pm)
+        if frame is not None:
+            dump_outputs(args.dump_outputs, frame)
         # (RCCL writes a version banner to C stdout when a communicator is made; through a pipe it would come out
         #  at exit, BEHIND the line: everything buffered so far goes first, the JSON line is the last one printed)
         sys.stdout.flush()
@@ -622,7 +511,7 @@ def main() -> int:
         # the frame of one more step of the main workload (config 5 may have run in between)
         import numpy as np
 
-        job2 = job if args.no_config5 else Job(pm, pmd, torch, dist, r, wl, rank, world, local, args)
+        job2 = Job(pm, pmd, torch, dist, r, wl, rank, world, local, args) if run_config5 else job
         if world > 1:
             job2.fence()
             if rank == 0:
@@ -638,6 +527,184 @@ def main() -> int:
         dist.destroy_process_group()
     r.close()
     return 0
+
+
+def last_frame(job, r):
+    """The frame the last step left on rank 0 (the sustained loop has fenced): the final image, gathered at N > 1."""
+    return job.full.cpu().numpy() if job.world > 1 else r.read_pixels()
+
+
+DUMP_SAMPLE_PIXELS = 3 << 20  # 48 MiB of float32 RGBA
+DUMP_SEED = 0x5EED0D
+
+
+def dump_sample_index(n_pixels):
+    """Row-major indices of the pixels --dump-outputs keeps: all of them, or DUMP_SAMPLE_PIXELS drawn with a fixed seed."""
+    import numpy as np
+
+    if n_pixels <= DUMP_SAMPLE_PIXELS:
+        return np.arange(n_pixels)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_pixels, DUMP_SAMPLE_PIXELS, replace=False))
+
+
+def dump_outputs(d, frame):
+    """DIR/frame.npy: float32 [n, 4], the RGBA8 values (0..255) of the pixels dump_sample_index picks -- the same pixels for the same
+    viewport in every run, so that two builds compare pixel for pixel."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    flat = frame.reshape(-1, 4)
+    np.save(os.path.join(d, "frame.npy"), flat[dump_sample_index(flat.shape[0])].astype(np.float32))
+
+
+def headline(args, job, world, value, t_frame, ms_per_step, sustained, workload_name, st, precondition, lat_iters):
+    """The result line of every run: the headline figure, the sustained rate, the workload and its scene."""
+    wl = job.wl
+    W, H = wl.width, wl.height
+    return {
+        "metric": "Mpixels/s, Ghostscript Tiger 3840x2160 (fills+strokes): W*H / t_frame" if args.workload == "config3" else f"Mpixels/s, {workload_name}: W*H / t_frame",
+        "value": round(value, 1), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "t_frame_ms": round(t_frame, 5),
+        "value_definition": ("W*H / t_frame; t_frame = one frame alone, first kernel begin to last kernel end: two HIP events on the frame's stream "
+                             f"around the plain launches pm_render makes (pm_frame_latency), median of {lat_iters} (SURVEY.md 8d)") if world == 1 else
+                            ("W*H / t_frame; t_frame = one step alone -- band render + gather into the final image on rank 0 -- between two events on "
+                             "the frame's stream (the GPU clock of the N=1 figure), median, MAX over ranks; t_frame_host_ms / config.t_frame_e2e_ms is the "
+                             "same step host-timed incl. launch latency and the device sync"),
+        "sustained_mpix_s": round(sustained, 1), "ms_per_step": round(ms_per_step, 5),
+        "sustained_definition": "W*H / (wall time of the K timed steps / K), steps submitted back to back, barrier + device sync on both sides, MAX over ranks"
+                                + ("" if world == 1 else "; every step ends with the gather to rank 0"),
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f32 geometry + f16 accumulators (as the reference)", "data": {"config2": "synthetic: embedded Ghostscript_Tiger.svg, scale 5.4, fills only, flattened on device",
+                                                                            "config3": "synthetic: embedded Ghostscript_Tiger.svg, scale 10.8, flattened on device",
+                                                                            "config4": "synthetic: 10 000 random closed cubic paths (SplitMix64 seed 0x5EED0004), flattened on device",
+                                                                            "config5": "synthetic: 5x5 grid of the embedded Ghostscript_Tiger.svg at scale 8, flattened on device",
+                                                                            "held1": "synthetic: embedded Ghostscript_Tiger.svg, scale 7.2, flattened on device",
+                                                                            "held2": "synthetic: 2 000 random closed cubic paths (SplitMix64 seed 0x5EED0008), flattened on device",
+                                                                            "held3": "synthetic: 20 000 glyph-like closed paths (SplitMix64 seed 0x5EED0007), flattened on device"}[args.workload],
+        "config": {
+            "workload": workload_name,
+            "viewport": [W, H], "items": job.n_items, "scene_bytes": job.scene_bytes,
+            "parallelism": "1 GPU" if world == 1 else f"tile-row bands x{world} ({'near-equal' if args.equal_bands else 'cost-balanced'} cuts), scene replicated, "
+                           f"{ {'cabi': 'pm_gather (C ABI: grouped RCCL send/recv)', 'sendrecv': 'grouped send/recv (torch.distributed)', 'allgather': 'padded all-gather'}.get(job.gather_impl, job.gather_impl) } "
+                           "of the bands into the final image on rank 0 in every step",
+            "gather_impl": None if world == 1 else job.gather_impl,
+            "gather_chunks": None if world == 1 else max(1, len(job.chunks)),
+            "band_cuts": job.cuts, "balance": job.balance_log or None,
+            # (what t_gather cannot beat: the largest non-root band over one xGMI link at ~153 GB/s; launch latency comes on top)
+            "t_gather_wire_floor_ms": None if world == 1 else round(job.pmd.gather_wire_floor_ms(job.layout, W, world), 5),
+            **({"gather_fallback": job.gather_fallback} if world > 1 and getattr(job, "gather_fallback", "") else {}),
+            "queued_tiles_rank0": st["queued_tiles"], "precondition_steps": precondition,
+        },
+        "scene": {
+            "flatten_encode_ms": round(job.scene_t["flatten_encode_ms"], 4), "scene_index_host_ms": round(job.scene_t["scene_index_ms"], 4),
+            "arena_setup_host_ms": round(job.scene_t["arena_setup_ms"], 4), "first_frame_ms": round(job.first_frame_ms, 4),
+            "first_frame_parts": job.first_frame_parts,
+            "note": "once per scene, like the reference encodes once per resize (PietRenderer.m:145): flatten_encode = pm_flatten_and_encode's four kernels + "
+                    "their read-backs; scene_index = header/item read-back, validation, pm_index_kernel; arena_setup = per-(scene, viewport) sizing on the host, "
+                    "paid by the first frame; first_frame = all of it fused, resize -> first frame complete (host wall clock)",
+        },
+    }
+
+
+def full_report(out, args, job, torch, rank, world, local, W, px, t_frame, t_frame_host, t_render, t_gather, ms_per_step,
+                tm, alone, n_overlapped, n_serial, rccl, cfg5, pm):
+    """--full: the headline line and what it does not need -- the same step host-timed, render and gather apart, the RCCL
+    binding, per-kernel durations and the roofline, config 5, the CPU baseline."""
+    rows = job.layout[rank][2]
+    b_alg = job.scene_bytes + 4 * W * rows  # this rank's launch: scene read once + its pixels written once
+    b_alg_frame = world * job.scene_bytes + 4 * px
+    kernels = {"pm_bin_kernel": tm["bin_ms"], "pm_coarse_kernel": tm["coarse_ms"], "pm_fine_kernel": tm["fine_ms"], "pm_clear_kernel": tm["clear_ms"]}
+    alone_ms = {"pm_bin_kernel": alone["bin_ms"], "pm_coarse_kernel": alone["coarse_ms"], "pm_fine_kernel": alone["fine_ms"], "pm_clear_kernel": alone["clear_ms"]}
+    if kernels["pm_clear_kernel"] == 0:  # folded into pm_fine_kernel's launch
+        kernels.pop("pm_clear_kernel")
+    if alone_ms["pm_clear_kernel"] == 0:  # (a frame alone folds it by default, frames behind others do not)
+        alone_ms.pop("pm_clear_kernel")
+    if kernels["pm_coarse_kernel"] == 0:  # fused: pm_fine_kernel<true> builds each tile's list itself
+        kernels.pop("pm_coarse_kernel")
+        alone_ms.pop("pm_coarse_kernel")
+    # the dominant kernel and its duration: kernels serialized on one stream, every launch alone on the
+    # GPU (a duration that fits inside a step; with four frames in flight the launches stretch each
+    # other and their in-flight durations exceed ms_per_step: kept below as *_inflight)
+    dom = max(alone_ms, key=alone_ms.get)
+    dom_ms = alone_ms[dom]
+    achieved = b_alg / (dom_ms * 1e-3) / 1e9
+    dom_inflight_ms = kernels[dom]
+    pipelined_ms = tm["total_ms"] / tm["iters"]
+    traffic, traffic_frame, issue, traffic_meta = None, None, None, None
+    # (one committed PMC digest per workload: the Tiger's is hbm_traffic.json, the others' hbm_traffic_<workload>.json)
+    tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json" if args.workload == "config3" else f"hbm_traffic_{args.workload}.json")
+    if os.path.exists(tpath) and world == 1:
+        try:
+            prof = json.load(open(tpath))
+            # the PMC figures are copied from a committed profile, not measured in this run: say which
+            # kernels they were taken on, and whether those are the kernels running now
+            sys.path.insert(0, os.path.join(ROOT, "tools"))
+            from make_traffic import kernel_sources_sha16
+
+            now = kernel_sources_sha16()
+            traffic_meta = {"source": prof.get("_source"), "measured_at_commit": prof.get("_commit"),
+                            "kernel_sources_sha16": prof.get("_kernel_sources_sha16"), "kernel_sources_sha16_now": now,
+                            "stale": prof.get("_kernel_sources_sha16") != now}
+            if traffic_meta["stale"]:
+                print(f"bench.py: profiles/hbm_traffic.json was measured on other kernel sources ({prof.get('_kernel_sources_sha16')} at commit "
+                      f"{prof.get('_commit')}, now {now}): roofline.traffic / issue_roofline are from that profile", file=sys.stderr)
+            traffic = prof.get(dom, {}).get("hbm_bytes_per_launch")
+            # (the counted runs pin PM_FOLD_CLEAR=1, tools/prof_round.sh: a frame is the launches a frame ALONE
+            #  makes, clearing inside the tile kernel's -- a separate pm_clear_kernel moves the same bytes)
+            counted = [k for k in alone_ms if k != "pm_clear_kernel"]
+            per_kernel = [prof[k]["hbm_bytes_per_launch"] for k in counted if "hbm_bytes_per_launch" in prof.get(k, {})]
+            if len(per_kernel) == len(counted):
+                traffic_frame = {"hbm_bytes_per_frame": int(sum(per_kernel)), "ratio_to_algorithmic": round(sum(per_kernel) / b_alg, 3)}
+            insts = sum(prof[k]["valu_insts_per_launch"] for k in counted if "valu_insts_per_launch" in prof.get(k, {}))
+            props = torch.cuda.get_device_properties(local)
+            n_simd = props.multi_processor_count * 4
+            clock_ghz = getattr(props, "clock_rate", 2400000) / 1e6
+            if insts:
+                # CDNA4 SIMDs are 32 lanes wide: a wave64 VALU instruction issues in 2 cycles
+                # (MI355X_MICROARCH.md, per-instruction constants); counts = SQ_INSTS_VALU of
+                # the committed PMC passes, one launch of each kernel = one frame
+                floor_ms = insts * 2 / n_simd / (clock_ghz * 1e9) * 1e3
+                issue = {"bound": "valu-issue", "valu_wave_insts_per_frame": insts, "simds": n_simd, "cycles_per_inst": 2,
+                         "clock_ghz": round(clock_ghz, 3), "floor_ms": round(floor_ms, 5),
+                         "frac_sustained": round(floor_ms / ms_per_step, 4), "frac_lone_frame": round(floor_ms / t_frame, 4),
+                         "source": prof.get("_source")}
+        except Exception:
+            traffic, traffic_frame, issue = None, None, None
+    out["t_frame_host_ms"] = round(t_frame_host, 5)
+    out["config"].update({
+        "rccl_lib": rccl.get("rccl_lib"), "rccl_ranks": rccl.get("rccl_ranks"), **({"rccl_error": rccl["rccl_error"]} if "rccl_error" in rccl else {}),
+        "t_render_ms": round(t_render, 5), "t_gather_ms": round(t_gather, 5), "t_frame_e2e_ms": round(t_frame_host, 5),
+    })
+    out["roofline"] = {
+        "bound": "hbm", "kernel": dom, "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+        "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_frame": traffic_frame, "traffic_profile": traffic_meta,
+        "algorithmic_bytes_per_launch": b_alg, "kernel_ms": round(dom_ms, 5),
+        "kernels_alone_ms": {k: round(v, 5) for k, v in alone_ms.items()},
+        "kernels_inflight_ms": {k: round(v, 5) for k, v in kernels.items()},
+        "frac_inflight": round(b_alg / (dom_inflight_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+        "frac_serial_frame": round(b_alg / (sum(alone_ms.values()) * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+        "trace_average_ms": {k: round((n_overlapped * kernels[k] + n_serial * alone_ms.get(k, 0.0)) / (n_overlapped + (n_serial if k in alone_ms else 0)), 5) for k in kernels},
+        "trace_average_note": "what the AverageNs column of a kernel trace of THIS command shows: the mix of in-flight and serialized launches it makes",
+        "frame_latency_ms": round(t_render, 5),
+        "frac_frame": round(b_alg_frame / world / (t_render * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+        "frame_pipelined_ms": round(pipelined_ms, 5),
+        "frac_frame_pipelined": round(b_alg / (pipelined_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+        "note": "frac credits the whole frame's bytes to ONE of the frame's kernels; frac_serial_frame = the same bytes / the SUM of the kernels' serialized "
+                "durations (the frame's kernels back to back, no gaps) and frac_frame = / the lone frame: read those as the path's fraction of HBM peak. "
+                "achieved/frac: algorithmic bytes of one launch / the dominant kernel's average launch duration with the kernels serialized on one "
+                "stream, events carried by the dispatches (what a rocprofv3 --kernel-trace of PM_FRAME_STREAMS=1 PM_SLOTS=1 shows: "
+                "profiles/*_serial_kernel_stats.csv); frac_inflight / kernels_inflight_ms: the same launches inside the overlapping batch of the "
+                "timed steps (four frames in flight: the durations stretch each other and exceed ms_per_step; what the default kernel trace "
+                "shows); frac_frame: B_alg(N)/N / the slowest rank's lone-frame time (SURVEY 8d multi-GPU roofline); frac_frame_pipelined: "
+                "B_alg / ms_per_step; the path is latency bound, not HBM bound (DESIGN.md)",
+    }
+    if issue is not None:
+        out["issue_roofline"] = issue
+    if cfg5 is not None:
+        out["config5"] = cfg5
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(pm, pm.workloads.tiger(3840, 2160))
+    return out
 
 
 def config5_block(pm, pmd, torch, dist, r, rank, world, local, args):

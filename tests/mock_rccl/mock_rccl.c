@@ -4,8 +4,11 @@
  * point-to-point messages travel as files in the directory PM_MOCK_RCCL_DIR names (one per (source,
  * destination, sequence number)); receives posted inside a group complete at ncclGroupEnd, sends at once
  * -- enough to exercise the argument, offset and grouping logic of pm_comm_* / pm_gather across real
- * processes.  Nothing here is RCCL, nothing here is measured. */
+ * processes.  Nothing here is RCCL, nothing here is measured.
+ * The directory may be longer than a unique id (a test's tmp_path under a long TMPDIR): the id carries its
+ * first 127 bytes, and every rank takes the whole path from its own PM_MOCK_RCCL_DIR, which must match. */
 #define _GNU_SOURCE
+#include <limits.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -18,7 +21,7 @@ typedef int ncclDataType_t;
 typedef struct { char internal[128]; } ncclUniqueId;
 struct mock_comm {
     int rank, world;
-    char dir[96];
+    char dir[PATH_MAX];
     unsigned send_seq[64], recv_seq[64];
 };
 typedef struct mock_comm *ncclComm_t;
@@ -34,7 +37,7 @@ const char *ncclGetErrorString(ncclResult_t e) { return e == 0 ? "no error" : "m
 
 ncclResult_t ncclGetUniqueId(ncclUniqueId *id) {
     const char *dir = getenv("PM_MOCK_RCCL_DIR");
-    if (!dir || strlen(dir) >= 96) return 2;
+    if (!dir || !*dir || strlen(dir) >= PATH_MAX) return 2;
     memset(id, 0, sizeof(*id));
     snprintf(id->internal, sizeof(id->internal), "%s", dir);
     return 0;
@@ -48,12 +51,14 @@ ncclResult_t ncclCommInitRank(ncclComm_t *comm, int world, ncclUniqueId id, int 
         const char *f = getenv("PM_MOCK_RCCL_FAIL_INIT");
         if (f && *f && (strcmp(f, "all") == 0 || atoi(f) == rank)) return 2;
     }
+    const char *dir = getenv("PM_MOCK_RCCL_DIR");
+    id.internal[sizeof(id.internal) - 1] = 0;
+    if (!dir || !*dir || strlen(dir) >= PATH_MAX || strncmp(dir, id.internal, strlen(id.internal)) != 0) return 4; /* not this job's id */
     struct mock_comm *c = (struct mock_comm *)calloc(1, sizeof(*c));
     if (!c) return 2;
     c->rank = rank;
     c->world = world;
-    id.internal[95] = 0;
-    snprintf(c->dir, sizeof(c->dir), "%s", id.internal);
+    snprintf(c->dir, sizeof(c->dir), "%s", dir);
     *comm = c;
     return 0;
 }
@@ -70,7 +75,7 @@ ncclResult_t ncclCommDestroy(ncclComm_t comm) {
 }
 
 static ncclResult_t do_recv(const struct pending *p) {
-    char path[192];
+    char path[PATH_MAX + 64];
     snprintf(path, sizeof(path), "%s/msg_%d_%d_%u.bin", p->comm->dir, p->peer, p->comm->rank, p->comm->recv_seq[p->peer]);
     for (int tries = 0; tries < 30000; ++tries) { /* 30 s */
         FILE *f = fopen(path, "rb");
@@ -110,7 +115,7 @@ ncclResult_t ncclGroupEnd(void) {
 ncclResult_t ncclSend(const void *buf, size_t count, ncclDataType_t t, int peer, ncclComm_t comm, hipStream_t s) {
     (void)s;
     if (!comm || peer < 0 || peer >= comm->world) return 4;
-    char tmp[200], path[192];
+    char tmp[PATH_MAX + 72], path[PATH_MAX + 64];
     snprintf(path, sizeof(path), "%s/msg_%d_%d_%u.bin", comm->dir, comm->rank, peer, comm->send_seq[peer]);
     snprintf(tmp, sizeof(tmp), "%s.tmp", path);
     FILE *f = fopen(tmp, "wb");

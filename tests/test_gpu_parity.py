@@ -559,7 +559,7 @@ def test_bench_two_rank_path_rehearsal_on_one_gpu(pm, pmo, tmp_path, chunks):
     dump = tmp_path / "frame.npy"
     env = dict(os.environ, PM_BENCH_SHARE_DEVICE="1", PM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(29517 + chunks), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-config5",
+           "--master-port", str(29517 + chunks), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-config5",
            "--gather-chunks", str(chunks), "--dump", str(dump)]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]

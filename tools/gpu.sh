@@ -13,7 +13,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 cd $ROOT; mkdir -p gpurun_out; export TMPDIR=/tmp
 TASK=${1:-tests}; shift
 digest='import json,sys
-j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j["roofline"]
+j=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=j.get("roofline") or {}  # (the roofline: --full runs only)
 print("value", j["value"], "t_frame", j["t_frame_ms"], "sustained", j["sustained_mpix_s"], "ms_per_step", j["ms_per_step"], "alone", r.get("kernels_alone_ms"), "frac", r.get("frac"), "frac_frame", r.get("frac_frame"), "cfg5", (j.get("config5") or {}).get("value"))'
 case $TASK in
 tests)
@@ -43,7 +43,7 @@ bench)
 ab)
   V=$1; R=$2; shift; shift
   for i in $(seq 1 $R); do for v in "" $V; do
-    PM_LIB_DEV=1 PM_LIB_VARIANT=$v timeout 300 python bench.py --steps 300 --warmup 40 --no-cpu-baseline --no-config5 "$@" 2>/dev/null | python -c "$digest" | sed "s/^/[${v:-base}] /"
+    PM_LIB_DEV=1 PM_LIB_VARIANT=$v timeout 300 python bench.py --full --steps 300 --warmup 40 --no-cpu-baseline --no-config5 "$@" 2>/dev/null | python -c "$digest" | sed "s/^/[${v:-base}] /"
   done; done | tee gpurun_out/ab.log ;;
 timelines)
   { for cfg in ${@:-config3}; do

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round profile (run on the GPU box through gpurun):  tools/prof_round.sh <tag>
-#   1. bench.py (default flags) -> gpurun_out/<tag>/bench.json
+#   1. bench.py --full (default flags otherwise) -> $OUT/bench.json
 #   2. rocprofv3 --kernel-trace --stats of the same command -> kernel_stats.csv (+ that run's own
 #      JSON line -> bench_traced.json); again with PM_FRAME_STREAMS=1 PM_SLOTS=1 -> serial_kernel_stats.csv
 #      (+ bench_serial_traced.json): launches that do not overlap
@@ -12,7 +12,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $ROOT/bench.py"
+BENCH="python $ROOT/bench.py --full"
 WL=${PM_PROF_FLAGS:---no-config5}   # the traced / counted runs hold ONE workload: kernel averages are per configuration
 timeout 900 $BENCH ${PM_PROF_MAIN:-} > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"; tail -c 1500 $OUT/bench.json
 # the traced run's own JSON line is kept next to the stats: same process, same launches
