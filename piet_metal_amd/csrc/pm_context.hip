@@ -700,6 +700,10 @@ int EnsureArena(pm_ctx *c) {
     // Which strip rows are cut in two (bin_split_mode): the heaviest ones, as many as the resident grid has workgroups to spare.
     std::vector<uint8_t> cut(need.size(), 0);
     c->n_sr_split = 0;
+    // (the plan is made with the frames' report whether or not it can cut: a report is read back once per plan at most,
+    //  FeedBackStripRows -- round-6 advisor: scenes with per-tile-row item lists drained the pipeline every third frame)
+    const bool fed = c->fb_slots.size() == need.size();  // (frames of this scene and viewport have reported)
+    c->fb_applied = fed;
     if (may_split && !c->use_row_lists) {  // (per-tile-row item lists are addressed by entry of the one work list)
         size_t n_rows = 0;
         for (size_t i = 0; i < need.size(); ++i) n_rows += ((need[i] + 3u) & ~3ull) != c->sr_empty_dwords ? 1u : 0u;
@@ -709,13 +713,11 @@ int EnsureArena(pm_ctx *c) {
         const size_t resident = static_cast<size_t>(c->n_cus) * (per_cu ? per_cu : 5u) * static_cast<size_t>(c->bin_split_fill) / 16u;
         const size_t room = c->bin_split_mode == 2 ? need.size() : (resident > n_rows ? resident - n_rows : 0u);
         std::vector<std::pair<uint32_t, uint32_t>> heavy;  // {weight, strip row}
-        const bool fed = c->fb_slots.size() == need.size();  // (frames of this scene and viewport have reported)
         for (size_t i = 0; i < need.size() && room != 0; ++i) {
             if (((need[i] + 3u) & ~3ull) == c->sr_empty_dwords) continue;
             if (c->bin_split_mode == 2) heavy.emplace_back(row_cands[i], static_cast<uint32_t>(i));
             else if (fed ? c->fb_slots[i] >= c->bin_split_slots : row_cands[i] >= c->bin_split_cands) heavy.emplace_back(fed ? c->fb_slots[i] : row_cands[i], static_cast<uint32_t>(i));
         }
-        c->fb_applied = fed;
         if (heavy.size() > room) {
             std::partial_sort(heavy.begin(), heavy.begin() + static_cast<ptrdiff_t>(room), heavy.end(),
                               [](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
@@ -828,6 +830,10 @@ int EnsureArena(pm_ctx *c) {
             if (!whole.empty() && (whole.back().x & 0xffff00ffu) == key) whole.back().z = desc[k].z;
             else whole.push_back(make_uint4(key | (15u << 12), desc[k].y, desc[k].z, 0u));
         }
+        // (chained for the plan's grid like the list with the cuts: frames that bind this list run min(grid, rows) groups, Enqueue,
+        //  and with more rows than the grid -- PM_BIN_SPLIT=2, or PM_BIN_WG_PER_CU=1 at 1080p -- a row past the grid is reached by
+        //  its chain only.  Round-6 advisor: unchained, those rows were never binned and their tiles stayed unrendered.)
+        for (size_t k = 0; k + c->bin_grid < whole.size(); ++k) whole[k].w = static_cast<uint32_t>(k + c->bin_grid);
         c->n_sr_whole = static_cast<uint32_t>(whole.size());
         if (!whole.empty()) PM_TRY(hipMemcpyAsync(c->d_sr_desc_whole, whole.data(), whole.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
     }
@@ -1154,7 +1160,9 @@ int FeedBackStripRows(pm_ctx *c) {
     if (c->frames_on_plan == 0xffffffffu) return PM_OK;
     c->frames_on_plan += 1;
     if (c->frames_on_plan != 3u || c->bin_split_mode != 1 || c->one_launch_mode != 0 || c->fb_applied || !c->d_sr_slots) return PM_OK;
-    // (only where cutting can happen at all: the plan's rows leave workgroups of the resident grid free)
+    // (only where cutting can happen at all: the plan's rows leave workgroups of the resident grid free, and the band bins from the
+    //  one work list -- per-tile-row item lists are addressed by its entries, EnsureArena cuts nothing)
+    if (c->use_row_lists) return PM_OK;
     if (c->n_sr_active >= static_cast<uint32_t>(c->n_cus) * (c->bin_wg_per_cu == 0xffu ? 5u : std::max(1u, c->bin_wg_per_cu))) return PM_OK;
     int r = SyncAll(c);
     if (r != PM_OK) return r;

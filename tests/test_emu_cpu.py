@@ -22,14 +22,14 @@ SUBSET = ("random_scenes or many_items or longer_than or empty_scene or even_odd
           "or heavy_strip_rows and 1-None or workgroup_tile_fills or dense_fill_pairs")
 
 
-def _run(k, extra_env=None, workers="4"):
+def _run(k, extra_env=None, workers="4", test_file="test_gpu_parity.py"):
     import torch
 
     if torch.cuda.is_available():
         pytest.skip("a GPU is present: the gpu-marked tests run on the real library")
     env = dict(os.environ, PM_TEST_EMU="1")
     env.update(extra_env or {})
-    cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_parity.py"), "-q", "-x", "-m", "gpu", "-k", k,
+    cmd = [sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", test_file), "-q", "-x", "-m", "gpu", "-k", k,
            "-p", "no:cacheprovider"]
     if workers:
         cmd += ["-n", workers]
@@ -73,4 +73,17 @@ def test_dense_tile_kernel_under_emulation(built):
     two-CU "device" with PM_DENSE_FACTOR=64 a single long list makes a frame dense, so the frames behind the first one of the
     switch test's scenes run it -- same bytes, same lists (captured from the general instantiation)."""
     out = _run("every_frame_path and 0-1-1 or every_frame_path and 2-1-1", {"PM_DENSE_FACTOR": "64", "PM_EMU_CUS": "2", "PM_EXPECT_DENSE": "1"}, workers="")
+    assert " passed" in out and "failed" not in out
+
+
+def test_frame_sequences_under_emulation(built):
+    """tests/test_frame_sequences.py: every row of frame-path switches over the frame-sequence script.  On a two-CU "device" the
+    binning grid (ten workgroups) is smaller than every frame's strip rows, so chains are walked everywhere -- the frames in flight
+    that bind the list without the cuts included -- and a band's twelve strip rows lie between what can be cut and what reports
+    (PM_BIN_WG_PER_CU=7); at the default 256 CUs the rows fit the grid, and the plan is remade from the frames' own report (or,
+    with per-tile-row item lists, left alone)."""
+    out = _run("frame_sequence", {"PM_EMU_CUS": "2"}, test_file="test_frame_sequences.py")
+    assert " passed" in out and "failed" not in out
+    out = _run("frame_sequence and (row_lists or split2 or overflow or pairwise00 or pairwise03)",
+               test_file="test_frame_sequences.py")
     assert " passed" in out and "failed" not in out
