@@ -157,13 +157,17 @@ int64_t pmo_scene_from_paths(uint8_t *buf, size_t cap, const pmo_path *paths, si
                              const pmo_path_el *els, size_t n_els, const double affine[6],
                              uint32_t *n_items_out);
 
-/* Segments a cubic is cut into (kurbo to_quads' n, libm-free: smallest n >= 1 with n^6 >= x). */
+/* Segments a cubic is cut into (kurbo to_quads' n, libm-free): the smallest n >= 1 with
+ * P6(n) >= x, P6(n) = ((n*n)*(n*n))*(n*n) in binary64 (rounded above n ~ 406); 2^30 for
+ * x > 1e54 and +inf, 1 for NaN.  The device kernels, the host encoder and tests/np_scene.py
+ * count the same way. */
 size_t pmo_subdivision_count(double x);
 
 /* src/flatten.rs:10-47 on elements [el_begin, el_end) after `affine`.
  * Writes subpath point counts into sub_counts (cap sub_cap) and points (x,y
  * doubles) into pts (cap pts_cap points).  Returns number of subpaths or -1 if
- * a capacity was exceeded (counts are still returned in n_points_out). */
+ * a capacity was exceeded (counts are still returned in n_points_out; a curve
+ * that does not fit is counted without generating its points). */
 int64_t pmo_flatten_path(const pmo_path_el *els, uint32_t el_begin, uint32_t el_end,
                          const double affine[6], double tolerance, uint32_t *sub_counts,
                          size_t sub_cap, double *pts, size_t pts_cap, size_t *n_points_out);

@@ -344,7 +344,7 @@ typedef struct {
 } scratch;
 
 static int flatten_grow(const pmo_path_el *els, const pmo_path *p, const double affine[6],
-                        scratch *s, int64_t *n_sub, size_t *n_pts) {
+                        scratch *s, int64_t *n_sub, size_t *n_pts, size_t out_cap) {
     for (;;) {
         int64_t r = pmo_flatten_path(els, p->el_begin, p->el_end, affine, TOLERANCE,
                                      s->sub_counts, s->sub_cap, s->pts, s->pts_cap, n_pts);
@@ -353,6 +353,7 @@ static int flatten_grow(const pmo_path_el *els, const pmo_path *p, const double 
             return 0;
         }
         if (r == -2) return -1; /* malformed path (LineTo before MoveTo) */
+        if (*n_pts > out_cap / 8) return -1; /* more points than the output buffer could hold: not generated */
         /* capacity: grow and retry */
         size_t need_sub = (size_t)(p->el_end - p->el_begin) + 1;
         if (s->sub_cap < need_sub) {
@@ -385,7 +386,7 @@ int64_t pmo_scene_from_paths(uint8_t *buf, size_t cap, const pmo_path *paths, si
     for (size_t i = 0; i < n_paths; i++) {
         int64_t n_sub;
         size_t n_pts;
-        if (flatten_grow(els, &paths[i], affine, &s, &n_sub, &n_pts)) goto done;
+        if (flatten_grow(els, &paths[i], affine, &s, &n_sub, &n_pts, cap)) goto done;
         if (paths[i].flags & PMO_PATH_FILL) /* count_fill_items; a compound fill (extension D11) is one item */
             n_items += (paths[i].flags & PMO_PATH_COMPOUND) ? (size_t)(n_sub > 0) : (size_t)n_sub;
         if (paths[i].flags & PMO_PATH_STROKE) n_items += (size_t)n_sub; /* count_stroke_items */
@@ -397,7 +398,7 @@ int64_t pmo_scene_from_paths(uint8_t *buf, size_t cap, const pmo_path *paths, si
     for (size_t i = 0; i < n_paths; i++) {
         int64_t n_sub;
         size_t n_pts;
-        if (flatten_grow(els, &paths[i], affine, &s, &n_sub, &n_pts)) goto done;
+        if (flatten_grow(els, &paths[i], affine, &s, &n_sub, &n_pts, cap)) goto done;
         if (paths[i].flags & PMO_PATH_FILL) {
             /* encode_path, src/lib.rs:342-347 */
             const double *pp = s.pts;

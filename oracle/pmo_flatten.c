@@ -36,10 +36,13 @@ static double cubic_eval(double p0, double p1, double p2, double p3, double t) {
  * the count depend on the last ulp of somebody's libm (glibc here, the device's OCML there, Rust's
  * powf in the reference); the count is an integer property of x, so it is DEFINED without libm:
  * the smallest n >= 1 with n^6 >= x, n^6 = ((n*n)*(n*n))*(n*n) in binary64 (exact below 2^53,
- * monotone beyond).  pow() only supplies the starting guess.  Non-finite x: as the cast does. */
+ * monotone beyond).  pow() only supplies the starting guess.  Above n ~ 406, n^6 > 2^53 and the
+ * product rounds: the rule is the binary64 product, not the exact integer (tests/np_scene.py).
+ * x > 1e54 (+inf included) counts 2^30, NaN counts 1 -- as the device kernels and the host encoder
+ * (a curve of 2^30 points cannot be stored in a scene of 4 GiB anyway). */
 size_t pmo_subdivision_count(double x) {
-    if (!(x > 1.0)) return 1;           /* also NaN */
-    if (x > 1e96) return (size_t)1e16;  /* (inf as usize saturates in Rust; never reached by real paths) */
+    if (!(x > 1.0)) return 1;               /* also NaN */
+    if (x > 1e54) return (size_t)1 << 30;   /* (never reached by a scene that fits) */
     double g = ceil(pow(x, 1.0 / 6.0));
     uint64_t n = g >= 1.0 ? (uint64_t)g : 1;
 #define P6(v) ((((double)(v)) * ((double)(v))) * (((double)(v)) * ((double)(v))) * (((double)(v)) * ((double)(v))))
@@ -110,6 +113,12 @@ int64_t pmo_flatten_path(const pmo_path_el *els, uint32_t el_begin, uint32_t el_
                 double dx = bx - ax, dy = by - ay;
                 double err = dx * dx + dy * dy;
                 size_t n = pmo_subdivision_count(err / max_hypot2); /* (ceil(x^(1/6)) as usize).max(1) */
+                if (n_pts + n > pts_cap) { /* no room: counted, not generated (n goes up to 2^30) */
+                    overflow = 1;
+                    n_pts += n;
+                    cur_n += (uint32_t)n;
+                    n = 0;
+                }
                 for (size_t k = 0; k < n; k++) {
                     double t1 = (double)(k + 1) / (double)n;
                     double x = cubic_eval(lx, p1x, p2x, p3x, t1);

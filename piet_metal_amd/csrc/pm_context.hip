@@ -2037,8 +2037,9 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
         r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, affine, width_scale, c->d_scene_alt,
                                       c->dev_scene_alt_cap, &bytes, &items, &he);
     if (r == PM_ERR_CAPACITY && bytes > c->dev_scene_alt_cap) {
-        // grow it (the kernels write it; nothing is staged on the host) and retry once
-        r = grow_alt(bytes + (bytes >> 3));
+        // grow it (the kernels write it; nothing is staged on the host) and retry once.  `bytes` is the exact need (the point count
+        // behind it is summed in 64 bits): beyond 4 GiB - 1 grow_alt refuses it; the headroom never makes a need that fits not fit.
+        r = grow_alt(std::max<size_t>(bytes, std::min<size_t>(bytes + (bytes >> 3), 0xffffffffull)));
         if (r == PM_OK)
             r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, affine, width_scale, c->d_scene_alt,
                                           c->dev_scene_alt_cap, &bytes, &items, &he);

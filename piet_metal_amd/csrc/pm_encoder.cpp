@@ -302,12 +302,19 @@ double HostCubicEval(double p0, double p1, double p2, double p3, double t) {  //
 // PM_ERR_INVALID: a LineTo / CurveTo before any MoveTo (the reference panics: cur_path.as_mut().unwrap()).
 // PM_ERR_CAPACITY: more points than `max_points` -- what the encoder's buffer could still hold; an
 // extreme (or NaN-adjacent) curve asks for up to 2^30 subdivisions, which must not be generated first.
+// The identity transform is APPLIED, as kurbo's Affine * Point does it (and the device kernels and the oracle): -0.0 becomes
+// +0.0, and an infinite coordinate makes the other one NaN (0 * inf).
 int HostFlatten(const pm_path_el *els, size_t n_els, size_t max_points, std::vector<double> *pts, std::vector<uint32_t> *sub_counts) {
     constexpr double kTolerance = 0.1;  // src/lib.rs:330
     bool open = false;
     double lx = 0.0, ly = 0.0;
     for (size_t i = 0; i < n_els; ++i) {
-        const pm_path_el &el = els[i];
+        pm_path_el el = els[i];
+        for (int k = 0; k < 6; k += 2) {
+            const double x = el.p[k], y = el.p[k + 1];
+            el.p[k] = 1.0 * x + 0.0 * y + 0.0;
+            el.p[k + 1] = 0.0 * x + 1.0 * y + 0.0;
+        }
         if (el.tag == PM_EL_MOVE) {
             sub_counts->push_back(1);
             open = true;

@@ -21,6 +21,7 @@
 
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 
 #include "../../include/piet_metal_amd.h"
 #include "pm_flatten.h"
@@ -80,7 +81,7 @@ __device__ __forceinline__ double CubicEval(double p0, double p1, double p2, dou
 // n^6 = ((n*n)*(n*n))*(n*n) in binary64.  pow() only supplies the starting guess.
 __device__ __forceinline__ uint32_t SubdivisionCount(double x) {
     if (!(x > 1.0)) return 1u;
-    if (x > 1e54) return 1u << 30;  // (no viewport-sized path gets here; keeps the arithmetic below in range)
+    if (x > 1e54) return 1u << 30;  // (also +inf; no scene that fits in 4 GiB gets here; keeps the arithmetic below in range)
     const double g = ceil(pow(x, 1.0 / 6.0));
     unsigned long long n = g >= 1.0 ? static_cast<unsigned long long>(g) : 1ull;
     auto p6 = [](unsigned long long v) {
@@ -92,52 +93,73 @@ __device__ __forceinline__ uint32_t SubdivisionCount(double x) {
     return static_cast<uint32_t>(n);
 }
 
+// Encoded points of an element: its points once per copy (fill, stroke) plus, for a MoveTo of a compound fill, the separator
+// behind its sub-path -- what KScan's 32-bit sums add up per path.  KCount sums them in 64 bits (*n_pts64): a single curve asks
+// for up to 2^30 points, and 32-bit sums of such counts wrap.
+__device__ __forceinline__ unsigned long long EncodedPoints(uint32_t flags, uint32_t n, uint32_t mv) {
+    const bool fill = (flags & PM_PATH_FILL) != 0, stroke = (flags & PM_PATH_STROKE) != 0;
+    return static_cast<unsigned long long>(n) * ((fill ? 1u : 0u) + (stroke ? 1u : 0u)) + ((fill && (flags & PM_PATH_COMPOUND) && mv) ? 1u : 0u);
+}
+
+// The scene these counts describe does not fit in scene_cap: KPoints and KItems then do nothing (a curve's count goes up to 2^30,
+// which one thread must not evaluate before the host learns that the scene cannot be stored anyway).
+__device__ __forceinline__ bool Overfull(uint32_t n_items, unsigned long long n_pts64, uint32_t scene_cap) {
+    return sizeof(SimpleGroup) + static_cast<unsigned long long>(n_items) * (sizeof(ShortBbox) + kItemSize) + 8ull * n_pts64 > scene_cap;
+}
+
 __global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
-                       uint32_t *el_npts, uint32_t *el_move, uint32_t *err) {
+                       uint32_t *el_npts, uint32_t *el_move, uint32_t *err, unsigned long long *n_pts64) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n_els) return;
-    const uint32_t p = PathOf(paths, n_paths, i);
-    const uint32_t tag = els[i].tag;
-    uint32_t n = 0, mv = 0;
-    if (i >= paths[p].el_begin && i < paths[p].el_end) {
-        if (tag == PM_EL_MOVE) {
-            n = 1;
-            mv = 1;
-        } else if (tag == PM_EL_LINE || tag == PM_EL_CURVE) {
-            double lx, ly;
-            // a sub-path must have been opened (cur_path.as_mut().unwrap(), flatten.rs:24,:36)
-            // (a path that starts with a MoveTo -- every well-formed one -- answers with one load; walking back
-            //  to the sub-path's MoveTo is a chain of dependent loads as long as the sub-path: 32 us for the
-            //  Tiger's longest, the whole kernel's duration)
-            bool opened = i > paths[p].el_begin && els[paths[p].el_begin].tag == PM_EL_MOVE;
-            if (!opened) {
-                for (uint32_t j = i; j > paths[p].el_begin;) {
-                    --j;
-                    if (els[j].tag == PM_EL_MOVE) { opened = true; break; }
+    unsigned long long q = 0;
+    if (i < n_els) {
+        const uint32_t p = PathOf(paths, n_paths, i);
+        const uint32_t tag = els[i].tag;
+        uint32_t n = 0, mv = 0;
+        if (i >= paths[p].el_begin && i < paths[p].el_end) {
+            if (tag == PM_EL_MOVE) {
+                n = 1;
+                mv = 1;
+            } else if (tag == PM_EL_LINE || tag == PM_EL_CURVE) {
+                double lx, ly;
+                // a sub-path must have been opened (cur_path.as_mut().unwrap(), flatten.rs:24,:36)
+                // (a path that starts with a MoveTo -- every well-formed one -- answers with one load; walking back
+                //  to the sub-path's MoveTo is a chain of dependent loads as long as the sub-path: 32 us for the
+                //  Tiger's longest, the whole kernel's duration)
+                bool opened = i > paths[p].el_begin && els[paths[p].el_begin].tag == PM_EL_MOVE;
+                if (!opened) {
+                    for (uint32_t j = i; j > paths[p].el_begin;) {
+                        --j;
+                        if (els[j].tag == PM_EL_MOVE) { opened = true; break; }
+                    }
+                }
+                if (!opened) {
+                    atomicExch(err, 1u);
+                } else if (tag == PM_EL_LINE) {
+                    n = 1;
+                } else {
+                    LastPoint(els, paths[p].el_begin, i, aff, &lx, &ly);
+                    double p1x, p1y, p2x, p2y, p3x, p3y;
+                    Xform(aff, els[i].p[0], els[i].p[1], &p1x, &p1y);
+                    Xform(aff, els[i].p[2], els[i].p[3], &p2x, &p2y);
+                    Xform(aff, els[i].p[4], els[i].p[5], &p3x, &p3y);
+                    const double accuracy = kTolerance * 1e-2;  // flatten.rs:35
+                    const double max_hypot2 = 432.0 * accuracy * accuracy;
+                    const double ax = p1x * 3.0 - lx, ay = p1y * 3.0 - ly;
+                    const double bx = p2x * 3.0 - p3x, by = p2y * 3.0 - p3y;
+                    const double dx = bx - ax, dy = by - ay;
+                    const double e = dx * dx + dy * dy;
+                    n = SubdivisionCount(e / max_hypot2);
                 }
             }
-            if (!opened) {
-                atomicExch(err, 1u);
-            } else if (tag == PM_EL_LINE) {
-                n = 1;
-            } else {
-                LastPoint(els, paths[p].el_begin, i, aff, &lx, &ly);
-                double p1x, p1y, p2x, p2y, p3x, p3y;
-                Xform(aff, els[i].p[0], els[i].p[1], &p1x, &p1y);
-                Xform(aff, els[i].p[2], els[i].p[3], &p2x, &p2y);
-                Xform(aff, els[i].p[4], els[i].p[5], &p3x, &p3y);
-                const double accuracy = kTolerance * 1e-2;  // flatten.rs:35
-                const double max_hypot2 = 432.0 * accuracy * accuracy;
-                const double ax = p1x * 3.0 - lx, ay = p1y * 3.0 - ly;
-                const double bx = p2x * 3.0 - p3x, by = p2y * 3.0 - p3y;
-                const double dx = bx - ax, dy = by - ay;
-                const double e = dx * dx + dy * dy;
-                n = SubdivisionCount(e / max_hypot2);
-            }
         }
+        el_npts[i] = n;
+        el_move[i] = mv;
+        q = EncodedPoints(paths[p].flags, n, mv);
     }
-    el_npts[i] = n;
-    el_move[i] = mv;
+    // (whole waves: the sum over the wave, then one atomic per wave)
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d, 64);
+    if ((threadIdx.x & 63u) == 0 && q != 0) atomicAdd(n_pts64, q);
 }
 
 // One workgroup.  Exclusive scans with totals at index n.
@@ -336,17 +358,19 @@ __global__ __launch_bounds__(kScanThreads) void KScanApply(uint32_t n_els, uint3
 //  it launches the kernels that depend on them)
 __global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
                         const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
-                        const uint32_t *path_pt_base, const uint32_t *totals, uint8_t *scene, uint32_t scene_cap,
-                        double *el_bbox, uint32_t *sub_first_el) {
+                        const uint32_t *path_pt_base, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
+                        uint32_t scene_cap, double *el_bbox, uint32_t *sub_first_el) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_els) return;
     const uint32_t n_items = totals[0];
+    if (Overfull(n_items, *n_pts64, scene_cap)) return;
     const uint32_t n = el_npts[i];
     if (n == 0) return;
     const uint32_t p = PathOf(paths, n_paths, i);
     const pm_path path = paths[p];
     const uint32_t tag = els[i].tag;
     if (tag == PM_EL_MOVE) sub_first_el[el_mvoff[i]] = i;
+    if (!(path.flags & (PM_PATH_FILL | PM_PATH_STROKE))) return;  // (nothing of it is encoded: its counts are not bounded by scene_cap)
     const uint32_t path_pts = el_ptoff[path.el_end] - el_ptoff[path.el_begin];
     const uint32_t local = el_ptoff[i] - el_ptoff[path.el_begin];
     const size_t points_start = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize);
@@ -419,11 +443,11 @@ __device__ __forceinline__ void WaveBox(double &x0, double &y0, double &x1, doub
 __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale,
                        const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
                        const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
-                       const double *el_bbox, const uint32_t *totals, uint8_t *scene, uint32_t scene_cap) {
+                       const double *el_bbox, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene, uint32_t scene_cap) {
     const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // sub-path of this wave
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_items = totals[0], n_subs = totals[2];
-    if (s >= n_subs) return;  // (whole waves)
+    if (s >= n_subs || Overfull(n_items, *n_pts64, scene_cap)) return;  // (whole waves)
     (void)els;
     const uint32_t first = sub_first_el[s];
     const uint32_t p = PathOf(paths, n_paths, first);
@@ -627,6 +651,9 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         *scene_bytes = sizeof(SimpleGroup);
         *n_items_out = 0;
         cache->meta_bytes = 0;
+        cache->resident = true;  // (pm_reflatten of paths without elements: the empty group again)
+        cache->n_paths = n_paths;
+        cache->n_els = n_els;
         return PM_OK;
     }
 
@@ -661,6 +688,9 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         uint32_t *sub_first = path_pt_base + np;
         uint32_t *d_totals = sub_first + ne;
         uint32_t *d_err = d_totals + 4;
+        // the 64-bit sum of the encoded points (KCount) sits in the error word's three spare neighbours, 8-byte aligned
+        unsigned long long *d_pts64 = reinterpret_cast<unsigned long long *>((reinterpret_cast<uintptr_t>(d_err + 1) + 7u) & ~static_cast<uintptr_t>(7u));
+        const size_t pts64_word = static_cast<size_t>(reinterpret_cast<uint32_t *>(d_pts64) - d_totals);  // 5 or 6
         const size_t meta_want = std::min<size_t>(scene_cap, sizeof(SimpleGroup) + cache->max_items * (sizeof(ShortBbox) + kItemSize));
         if (meta_want + 32 > cache->cap_meta || !cache->h_meta) {
             if (cache->h_meta) (void)hipHostFree(cache->h_meta);
@@ -670,11 +700,11 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
             PM_HIP_TRY(hipHostMalloc(&cache->h_meta, want, hipHostMallocDefault));
             cache->cap_meta = want;
         }
-        uint32_t *h_totals = reinterpret_cast<uint32_t *>(cache->h_meta);  // [0..3] totals, [4] error flag; the scene head follows at +32
+        uint32_t *h_totals = reinterpret_cast<uint32_t *>(cache->h_meta);  // [0..3] totals, [4] error flag, [5..7] the 64-bit point sum; the scene head follows at +32
         PM_HIP_TRY(hipMemsetAsync(d_totals, 0, 8 * sizeof(uint32_t), stream));
         const uint32_t tb = 256;
         const uint32_t cap32 = static_cast<uint32_t>(std::min<size_t>(scene_cap, 0xffffffffull));
-        hipLaunchKernelGGL(KCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_move, d_err);
+        hipLaunchKernelGGL(KCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_move, d_err, d_pts64);
         if (ne <= ScanSplit()) {
             hipLaunchKernelGGL(KScan, dim3(1), dim3(kScanThreads), 0, stream, d_paths, np, ne, el_npts, el_move, el_ptoff, el_mvoff,
                                path_item_base, path_pt_base, d_totals);
@@ -693,12 +723,14 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         }
         hipLaunchKernelGGL(KHeader, dim3(1), dim3(1), 0, stream, d_scene, static_cast<const uint32_t *>(d_totals), 0u, cap32);
         hipLaunchKernelGGL(KPoints, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_ptoff,
-                           el_mvoff, path_pt_base, static_cast<const uint32_t *>(d_totals), d_scene, cap32, d_bbox, sub_first);
+                           el_mvoff, path_pt_base, static_cast<const uint32_t *>(d_totals), static_cast<const unsigned long long *>(d_pts64), d_scene, cap32, d_bbox,
+                           sub_first);
         // (a wave per sub-path; sub-paths <= elements)
         hipLaunchKernelGGL(KItems, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_npts, el_ptoff,
-                           el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals), d_scene, cap32);
+                           el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals),
+                           static_cast<const unsigned long long *>(d_pts64), d_scene, cap32);
         PM_HIP_TRY(hipGetLastError());
-        PM_HIP_TRY(hipMemcpyAsync(h_totals, d_totals, sizeof(uint32_t) * 5, hipMemcpyDeviceToHost, stream));
+        PM_HIP_TRY(hipMemcpyAsync(h_totals, d_totals, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, stream));
         PM_HIP_TRY(hipMemcpyAsync(cache->h_meta + 32, d_scene, meta_want, hipMemcpyDeviceToHost, stream));
         PM_HIP_TRY(hipStreamSynchronize(stream));
         cache->meta_bytes = 0;
@@ -707,7 +739,11 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
             goto fail;
         }
         const uint32_t n_items = h_totals[0];
-        const size_t need = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize) + static_cast<size_t>(h_totals[1]) * 8;
+        // (the encoded points from their 64-bit sum: h_totals[1], the 32-bit one, has wrapped when a scene asks for 2^32 of them;
+        //  where it fits in scene_cap the two are equal)
+        unsigned long long n_pts64 = 0;
+        std::memcpy(&n_pts64, h_totals + pts64_word, sizeof(n_pts64));
+        const size_t need = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize) + static_cast<size_t>(n_pts64) * 8;
         if (need > scene_cap || need > 0xffffffffull) {
             status = PM_ERR_CAPACITY;
             *scene_bytes = need;

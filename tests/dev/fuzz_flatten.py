@@ -8,40 +8,10 @@ import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 import piet_metal_amd as pm
-from piet_metal_amd import _lib
 from oracle import pmo
-
-
-def random_pathset(rng, n_paths, extent):
-    els, paths = [], []
-    for _ in range(n_paths):
-        e0 = len(els)
-        for _sub in range(int(rng.integers(1, 4))):
-            p = rng.uniform(0, extent, 2)
-            els.append((_lib.PM_EL_MOVE, [p[0], p[1], 0, 0, 0, 0]))
-            for _seg in range(int(rng.integers(1, 7))):
-                kind = rng.integers(0, 3)
-                step = float(rng.choice([3.0, 30.0, 150.0]))
-                q = [p + rng.uniform(-step, step, 2) for _ in range(3)]
-                if kind == 0:
-                    els.append((_lib.PM_EL_LINE, [q[0][0], q[0][1], 0, 0, 0, 0])); p = q[0]
-                elif kind == 1:
-                    els.append((_lib.PM_EL_QUAD, [q[0][0], q[0][1], q[1][0], q[1][1], 0, 0])); p = q[1]
-                else:
-                    els.append((_lib.PM_EL_CURVE, [q[0][0], q[0][1], q[1][0], q[1][1], q[2][0], q[2][1]])); p = q[2]
-            if rng.random() < 0.6:
-                els.append((_lib.PM_EL_CLOSE, [0] * 6))
-        flags = int(rng.integers(1, 4))  # fill, stroke or both
-        flags |= (4 if rng.random() < 0.3 else 0) | (8 if rng.random() < 0.4 else 0)  # even-odd rule, compound fill
-        rgba = lambda: (int(rng.integers(0, 1 << 24)) << 8 | (0xFF if rng.random() < 0.4 else int(rng.integers(1, 255)))) & 0xFFFFFFFF
-        width = float(rng.choice([0.05, 0.3, 1.0, 4.0]))
-        paths.append((e0, len(els), flags, rgba(), rgba(), width))
-    E = np.zeros(len(els), pm.PathSet.EL_DTYPE)
-    for i, (t, p) in enumerate(els):
-        E["tag"][i] = t; E["p"][i] = p
-    P = np.array(paths, dtype=pm.PathSet.PATH_DTYPE)
-    return pm.PathSet(P, E)
+from path_sets import random_pathset  # (shared with tests/test_flatten_edges.py)
 
 
 def main():

@@ -104,6 +104,10 @@ __attribute__((noinline)) static double __shfl_xor(double v, int lane_mask, int 
     std::memcpy(&out, &r, 8);
     return out;
 }
+__attribute__((noinline)) static unsigned long long __shfl_xor(unsigned long long v, int lane_mask, int width = 64) {
+    (void)width;
+    return pm_emu::Collective(pm_emu::kShfl, v, (pm_emu::LaneId() ^ static_cast<uint32_t>(lane_mask)) & 63u, 0, PM_EMU_SITE());
+}
 static inline double __longlong_as_double(long long v) { double d; std::memcpy(&d, &v, 8); return d; }
 __attribute__((noinline)) static void __builtin_amdgcn_wave_barrier() { (void)pm_emu::Collective(pm_emu::kWaveBarrier, 0, 0, 0, PM_EMU_SITE()); }
 __attribute__((noinline)) static void __syncthreads() { pm_emu::BlockBarrier(PM_EMU_SITE()); }

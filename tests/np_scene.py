@@ -7,9 +7,32 @@ Cross-checks oracle/pmo_flatten.c + pmo_encoder.c.  Test infrastructure.
 import math
 
 
+def p6(n):
+    """n^6 as the product computes it: ((n*n)*(n*n))*(n*n) in binary64 (exact up to n = 406, rounded above)."""
+    d = float(n)
+    return ((d * d) * (d * d)) * (d * d)
+
+
 def subdivision_count(x):
-    """kurbo to_quads' n = max(1, ceil(x^(1/6))) as an exact integer property of x: the smallest
-    n >= 1 with n^6 >= x (Python integers against the exact rational value of the double x)."""
+    """kurbo to_quads' n = max(1, ceil(x^(1/6))) as the product defines it, libm-free: the smallest
+    n >= 1 with p6(n) >= x; 2^30 for x > 1e54 (and +inf), 1 for NaN.  The rule of the device kernels,
+    the host encoder and the oracle (oracle/pmo.h).  Above n = 406 p6 rounds, and where p6(n) rounds up
+    past n^6 this n is one less than the exact-integer count (subdivision_count_exact)."""
+    if not x > 1.0:
+        return 1
+    if x > 1e54:
+        return 1 << 30
+    n = max(1, int(math.ceil(x ** (1.0 / 6.0))))
+    while n > 1 and p6(n - 1) >= x:
+        n -= 1
+    while p6(n) < x:
+        n += 1
+    return n
+
+
+def subdivision_count_exact(x):
+    """The same count in exact integers against the exact rational value of the double x: the smallest
+    n >= 1 with n^6 >= x.  Equal to subdivision_count wherever p6 is exact around the answer."""
     from fractions import Fraction
 
     if not x > 1.0:
@@ -21,6 +44,8 @@ def subdivision_count(x):
     while n ** 6 < fx:
         n += 1
     return n
+
+
 import struct
 
 import numpy as np

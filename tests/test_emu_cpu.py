@@ -38,6 +38,14 @@ def _run(k, extra_env=None, workers="4", test_file="test_gpu_parity.py"):
     return p.stdout
 
 
+def test_flatten_edges_under_emulation(built):
+    """tests/test_flatten_edges.py: the flatten kernels on the random path grammar (both prefix-sum variants), the edge-case table,
+    the exact-rational point check, and one curve of 2^30 points (infinite and 1e30 control points); not the 2^32-point path,
+    whose 4 096 curves the unfixed kernels would evaluate one lane after the other."""
+    out = _run("flatten_edges and not wrap", test_file="test_flatten_edges.py")
+    assert " passed" in out and "failed" not in out
+
+
 def test_parity_subset_under_wave64_emulation(built):
     out = _run(SUBSET)
     assert " passed" in out and "failed" not in out
