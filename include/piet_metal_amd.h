@@ -381,6 +381,29 @@ int pm_debug_capture_ptcl(pm_ctx *c, uint32_t max_cmds_per_tile, uint32_t *count
  * A validation call: it synchronises and rebuilds the scene index twice. */
 int pm_fill_coverage(pm_ctx *c, uint32_t item_ix, float *dst, size_t dst_stride_floats);
 
+/* ==== point hit testing (new: the reference has none; DESIGN.md 2, decision D13, says what "contains" means) ====
+ * Independent of pm_resize / pm_set_band / pm_set_target_format (a context with a scene and no viewport answers too);
+ * frames in flight are not disturbed. */
+#define PM_HIT_NONE 0xffffffffu
+#define PM_HIT_SKIP_TRANSPARENT 1u   /* items whose colour has alpha 0 are not hit (Circles are opaque black) */
+
+/* xy = n points {x, y} in scene coordinates (= pixels; the centre of pixel (px, py) is (px + 0.5, py + 0.5)).
+ * top_item[k] = index, in flat paint order (what pm_stats.n_items counts: nested groups inlined depth first),
+ * of the LAST-painted item that contains point k, or PM_HIT_NONE.  n_hit (may be NULL) = how many items contain it.
+ * A point with a non-finite coordinate hits nothing.  n == 0 is PM_OK; unknown flag bits and a context without a
+ * resident scene are PM_ERR_INVALID.  Synchronises. */
+int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *top_item, uint32_t *n_hit);
+
+/* Same on device memory (e.g. torch tensors), asynchronous on hip_stream (NULL: the context's stream).  It reads the scene
+ * that is resident when it is called: a later scene replacement waits for it before anything it reads is overwritten. */
+int pm_hit_test_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t flags,
+                       void *dev_top_item, void *dev_n_hit, void *hip_stream);
+
+/* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
+ * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
+ * from pm_upload_scene (or no scene at all). */
+int pm_item_paths(pm_ctx *c, uint32_t *path_of_item, size_t cap, uint32_t *n_items);
+
 /* Developer / test hook for the generated layout code (piet_metal_amd/csrc/pm_layout_gen.h, printed by
  * pm_layoutgen from piet_metal_amd/layout/piet_layout.pgpu -- the HIP / C++ target of the reference's
  * piet-gpu-derive generator, piet-gpu-derive/src/lib.rs): every item of `scene`'s root group and

@@ -33,6 +33,8 @@ PM_SVG_REJECT_ARC_PATHS = 1
 PM_SVG_SPEC_DEFAULTS = 2
 PM_SVG_FLAT_GRADIENTS = 4
 PM_FMT_RGBA8, PM_FMT_BGRA8 = 0, 1
+PM_HIT_NONE = 0xFFFFFFFF
+PM_HIT_SKIP_TRANSPARENT = 1
 
 
 class PathEl(C.Structure):
@@ -139,6 +141,9 @@ SIGNATURES = {
     "pm_debug_frame_timeline": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_float)]),
     "pm_get_stats": (C.c_int, [C.c_void_p, C.POINTER(Stats)]),
     "pm_fill_coverage": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t]),
+    "pm_hit_test": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_hit_test_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),
     "pm_get_binning_plans": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),

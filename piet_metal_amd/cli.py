@@ -4,6 +4,7 @@
     python -m piet_metal_amd.cli drawing.svg out.png --scale 4 --width 1024 --height 1024
 
     python -m piet_metal_amd.cli tiger spin.png --frames 60 --spin 360     (spin-000.png ... spin-059.png)
+    python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
 machine without a display: the frame is rendered on the MI355X by the same three kernels as
@@ -74,7 +75,14 @@ def main(argv=None) -> int:
     ap.add_argument("--no-flat-gradients", action="store_true", help="files: do not draw gradient paints at all (default: as the mean colour of their stops)")
     ap.add_argument("--frames", type=int, default=1, help="render an animation of this many frames (output NAME-###.png)")
     ap.add_argument("--spin", type=float, default=360.0, help="--frames: total rotation about the viewport centre, degrees")
+    ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
     args = ap.parse_args(argv)
+    try:
+        picks = [tuple(float(v) for v in p.split(",")) for p in args.pick]
+        if any(len(p) != 2 for p in picks):
+            raise ValueError
+    except ValueError:
+        ap.error("--pick takes X,Y")
 
     from . import PathSet, Renderer
 
@@ -94,6 +102,11 @@ def main(argv=None) -> int:
         nbytes, nitems = r.flatten_and_encode(paths, base, scale)
         r.render()
         img = r.read_pixels()
+        if picks:  # one line per point: the item in flat paint order and the <path> it came from, or none
+            top = r.hit_test(np.array(picks, np.float32))
+            of_item = r.item_paths()
+            for (x, y), t in zip(picks, top):
+                print(f"{x:g},{y:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
         if args.frames <= 1:
             write_png(args.output, img)
             print(f"{args.output}: {args.width}x{args.height}, {nitems} items, scene {nbytes} bytes", file=sys.stderr)

@@ -35,6 +35,7 @@
 #include "../../include/piet_metal_amd.h"
 #include "pm_device.h"
 #include "pm_flatten.h"
+#include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing, the one kernel of this unit
 #include "pm_layout.h"
 
 namespace {
@@ -323,6 +324,15 @@ struct pm_ctx {
     int last_slot = -1;  // slot of the most recently submitted frame
 
     pm::FlattenCache flatten_cache;  // resident paths + scratch of the flatten stage
+    bool scene_from_paths = false;   // the resident scene is the flatten kernels' (pm_item_paths maps its items to their paths)
+
+    // point hit testing (pm_hit_test / pm_hit_test_device): reads the scene and the scene index, nothing of a frame
+    hipEvent_t ev_scene = nullptr;     // end of what the last scene replacement left on `stream` (upload, index): a hit test on another stream starts behind it
+    hipEvent_t ev_hit = nullptr;       // end of the hit tests submitted so far; a scene replacement waits for it (SyncAll)
+    hipStream_t hit_stream = nullptr;  // the stream it was last recorded on (compared, never dereferenced)
+    bool hit_pending = false;          // a hit test was submitted since everything was last waited for
+    uint8_t *d_hit = nullptr;          // pm_hit_test's device staging: one batch of {xy, top_item, n_hit}
+    size_t hit_cap = 0;                // queries it holds
 
     // wall-clock cost of the last scene replacement, host view (pm_get_scene_timings)
     float t_flatten_ms = 0, t_index_ms = 0, t_arena_ms = 0;
@@ -353,6 +363,9 @@ int SyncAll(pm_ctx *c) {
         if (s.in_flight && s.user_stream) PM_TRY(hipEventSynchronize(s.ev_done));
         s.in_flight = false;
     }
+    // (hit tests on a caller's stream read the scene and its index like a frame does)
+    if (c->hit_pending) PM_TRY(hipEventSynchronize(c->ev_hit));
+    c->hit_pending = false;
     return PM_OK;
 }
 
@@ -1442,6 +1455,7 @@ int BuildSceneIndex(pm_ctx *c) {
     PM_TRY(hipMemcpyAsync(c->d_chunk_base, base.data(), base.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     pm::LaunchIndex(c->d_scene, n, c->dev_items_ix, c->d_chunk_base, c->n_chunks, c->d_chunk_bbox, c->d_sup_bbox, c->stream);
     PM_TRY(hipGetLastError());
+    PM_TRY(hipEventRecord(c->ev_scene, c->stream));  // (what a hit test on a caller's stream starts behind)
     // (no wait: frames run on streams that are ordered behind c->stream where it matters -- Enqueue below --
     //  and the next scene replacement starts with SyncAll before `base` is touched again)
     return PM_OK;
@@ -1456,6 +1470,7 @@ void InvalidateScene(pm_ctx *c) {
     c->n_items = 0;
     c->n_chunks = 0;
     c->item_meta.clear();
+    c->scene_from_paths = false;
     c->last_slot = -1;
     c->arena_dirty = true;
     for (auto &t : c->slot)  // (another scene: whether its frames are dense is for its own tile kernels to say)
@@ -1760,6 +1775,8 @@ pm_ctx *pm_create(int device, int *err) {
 
     for (auto &ev : c->ev)
         if ((e = hipEventCreate(&ev)) != hipSuccess) return fail(e, "hipEventCreate");
+    if ((e = hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
+    if ((e = hipEventCreateWithFlags(&c->ev_hit, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
     for (auto &s : c->slot) {
         if ((e = hipEventCreateWithFlags(&s.ev_done, hipEventDisableTiming)) != hipSuccess) return fail(e, "hipEventCreate");
         if ((e = hipMalloc(&s.d_ctr, 2 * sizeof(pm::Counters))) != hipSuccess) return fail(e, "hipMalloc(counters)");
@@ -1926,6 +1943,9 @@ void pm_destroy(pm_ctx *c) {
     if (c->d_lut_lin2srgb) (void)hipFree(c->d_lut_lin2srgb);
     for (auto &ev : c->ev)
         if (ev) (void)hipEventDestroy(ev);
+    if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
+    if (c->ev_hit) (void)hipEventDestroy(c->ev_hit);
+    if (c->d_hit) (void)hipFree(c->d_hit);
     for (hipStream_t q : c->streams) (void)hipStreamDestroy(q);
     delete c;
 }
@@ -2062,6 +2082,7 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
     c->t_flatten_ms = flatten_ms;
     r = SetScene(c, bytes, nullptr);
     if (r != PM_OK) return r;
+    c->scene_from_paths = true;
     if (scene_bytes) *scene_bytes = bytes;
     if (n_items) *n_items = items;
     return PM_OK;
@@ -2644,6 +2665,120 @@ int pm_fill_coverage(pm_ctx *c, uint32_t item_ix, float *dst, size_t dst_stride_
     const int rb = BuildSceneIndex(c);
     if (e != hipSuccess) return HipFail(e, "pm_fill_coverage");
     return status != PM_OK ? status : rb;
+}
+
+// ---- point hit testing (pm_hit_kernel, pm_hit_test.h) ----------------------------------------------------------------
+namespace {
+constexpr size_t kHitLaunchMax = static_cast<size_t>(1) << 30;  // queries per launch (the kernel indexes them in 32 bits)
+constexpr size_t kHitBatch = static_cast<size_t>(1) << 22;      // pm_hit_test: queries staged on the device at a time (64 MiB)
+
+int HitCheck(pm_ctx *c, uint32_t flags) {
+    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)) {
+        SetError("pm_hit_test: unknown flag bits");
+        return PM_ERR_INVALID;
+    }
+    if (!c->d_scene || c->scene_bytes < 8) {  // (what pm_render says: BuildParams)
+        SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// The launches for n queries in device memory, on q.  They read the scene buffer and the scene index as they are now: whatever
+// replaces them waits for ev_hit first (SyncAll).
+int HitEnqueue(pm_ctx *c, const float *d_xy, size_t n, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, hipStream_t q) {
+    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));  // the scene's upload and index ran on c->stream
+    // (ONE event stands for every hit test submitted: when it moves to another stream, that stream first waits for what it stood for)
+    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
+    pm::HitParams p{};
+    p.scene = c->d_scene;
+    p.n_items = c->n_items;
+    p.items_ix = c->dev_items_ix;
+    p.bbox_ix = c->dev_bbox_ix;
+    p.chunk_base = c->d_chunk_base;
+    p.chunk_bbox = c->d_chunk_bbox;
+    p.sup_bbox = c->d_sup_bbox;
+    p.flags = flags;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.xy = d_xy + 2 * at;
+        p.top_item = d_top + at;
+        p.n_hit = d_cnt ? d_cnt + at : nullptr;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchHitTest(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    PM_TRY(hipGetLastError());
+    PM_TRY(hipEventRecord(c->ev_hit, q));
+    c->hit_stream = q;
+    c->hit_pending = true;
+    return PM_OK;
+}
+}  // namespace
+
+int pm_hit_test_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t flags, void *dev_top_item, void *dev_n_hit, void *hip_stream) {
+    if (!c || (n != 0 && (!dev_xy || !dev_top_item))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    return HitEnqueue(c, static_cast<const float *>(dev_xy), n, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit),
+                      hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *top_item, uint32_t *n_hit) {
+    if (!c || (n != 0 && (!xy || !top_item))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    const size_t batch = std::min(n, kHitBatch);
+    if (batch > c->hit_cap) {  // {xy, top_item, n_hit}: 16 bytes per query
+        PM_TRY(hipStreamSynchronize(c->stream));
+        if (c->d_hit) (void)hipFree(c->d_hit);
+        c->d_hit = nullptr;
+        c->hit_cap = 0;
+        PM_TRY(hipMalloc(&c->d_hit, batch * 16));
+        c->hit_cap = batch;
+    }
+    float *d_xy = reinterpret_cast<float *>(c->d_hit);
+    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_hit + c->hit_cap * 8);
+    uint32_t *d_cnt = n_hit ? d_top + c->hit_cap : nullptr;
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(d_xy, xy + 2 * at, m * 8, hipMemcpyHostToDevice, c->stream));
+        r = HitEnqueue(c, d_xy, m, flags, d_top, d_cnt, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(top_item + at, d_top, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (n_hit) PM_TRY(hipMemcpyAsync(n_hit + at, d_cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+int pm_item_paths(pm_ctx *c, uint32_t *path_of_item, size_t cap, uint32_t *n_items) {
+    if (!c || !n_items) return PM_ERR_INVALID;
+    *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    if (c->scene_bytes < 8 || !c->scene_from_paths) {
+        SetError("pm_item_paths: the resident scene was not made by pm_flatten_and_encode / pm_reflatten");
+        return PM_ERR_INVALID;
+    }
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n == 0) return PM_OK;
+    if (!path_of_item) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    // KItems numbers a path's items from path_item_base[p] on (fills first, then strokes): the table is still where the scan left it
+    std::vector<uint32_t> base(c->flatten_cache.n_paths);
+    hipError_t he = hipSuccess;
+    const int r = pm::FlattenPathItemBases(c->stream, &c->flatten_cache, base.data(), &he);
+    if (r == PM_ERR_HIP) return HipFail(he, "pm_item_paths");
+    if (r != PM_OK) return r;
+    for (size_t p = 0; p < base.size(); ++p) {
+        const size_t end = p + 1 < base.size() ? base[p + 1] : n;
+        if (base[p] > end || end > n) {
+            SetError("pm_item_paths: the flatten stage's item table does not match the resident scene");
+            return PM_ERR_SCENE;
+        }
+        for (size_t i = base[p]; i < end; ++i) path_of_item[i] = static_cast<uint32_t>(p);
+    }
+    return PM_OK;
 }
 
 int pm_debug_capture_ptcl(pm_ctx *c, uint32_t max_cmds_per_tile, uint32_t *counts, uint32_t *solid, pm_cmd *cmds) {

@@ -37,4 +37,8 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
                           size_t n_els, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
                           size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error);
 
+// First item of every resident path in the scene the kernels last wrote (h_base: cache->n_paths entries; path p's items are
+// [h_base[p], h_base[p + 1]), the last path's end at the scene's item count).  Synchronises `stream`.
+int FlattenPathItemBases(hipStream_t stream, const FlattenCache *cache, uint32_t *h_base, hipError_t *hip_error);
+
 }  // namespace pm

@@ -764,4 +764,19 @@ fail:
     return status;
 }
 
+int FlattenPathItemBases(hipStream_t stream, const FlattenCache *cache, uint32_t *h_base, hipError_t *hip_error) {
+    if (!cache->resident) return PM_ERR_INVALID;
+    const size_t ne = cache->n_els, np = cache->n_paths;
+    if (np == 0 || ne == 0) return PM_OK;  // (the empty group: no kernel ran, no item to map)
+    // d_u32 as FlattenEncodeOnDevice lays it out: el_npts[ne], el_move[ne], el_ptoff[ne + 1], el_mvoff[ne + 1], path_item_base[np], ...
+    const uint32_t *path_item_base = cache->d_u32 + ne * 2 + (ne + 1) * 2;
+    hipError_t e = hipMemcpyAsync(h_base, path_item_base, np * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        if (hip_error) *hip_error = e;
+        return PM_ERR_HIP;
+    }
+    return PM_OK;
+}
+
 }  // namespace pm

@@ -220,6 +220,48 @@ class Renderer:
         _lib.check(self._lib.pm_fill_coverage(self._h, item_ix, out.ctypes.data, self.width), "pm_fill_coverage")
         return out
 
+    # ---- point hit testing ------------------------------------------------------------
+    def hit_test(self, points, skip_transparent: bool = False, counts: bool = False):
+        """The last-painted item under every point: `points` is (n, 2) float32 {x, y} in scene coordinates (pixel (px, py) has its
+        centre at (px + 0.5, py + 0.5)).  Returns top_item, uint32 [n] -- indices in flat paint order, PM_HIT_NONE (0xffffffff)
+        where nothing is hit --, and with counts=True also how many items contain each point.  Needs a scene, no viewport."""
+        xy = np.ascontiguousarray(points, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("hit_test needs an (n, 2) array of points")
+        n = xy.shape[0]
+        top = np.empty(n, np.uint32)
+        cnt = np.empty(n, np.uint32) if counts else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_test(self._h, xy.ctypes.data, n, flags, top.ctypes.data, cnt.ctypes.data if counts else None), "pm_hit_test")
+        return (top, cnt) if counts else top
+
+    def hit_test_tensor(self, xy, top_item, n_hit=None, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: xy float32 [n, 2], top_item (and n_hit) int32 or uint32 [n], all
+        contiguous.  `stream` as in render_to: None, or torch's legacy default stream (handle 0), means the context's OWN stream."""
+        if not (xy.is_cuda and top_item.is_cuda) or str(xy.dtype) != "torch.float32" or xy.dim() != 2 or xy.shape[1] != 2 or not xy.is_contiguous():
+            raise TypeError("hit_test_tensor needs a contiguous CUDA float32 tensor [n, 2]")
+        n = xy.shape[0]
+        for t in (top_item, n_hit):
+            if t is not None and not (t.is_cuda and t.element_size() == 4 and t.numel() == n and t.is_contiguous()):
+                raise TypeError("hit_test_tensor writes contiguous CUDA tensors of n 32-bit integers")
+        s = stream.cuda_stream if stream is not None else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_test_device(self._h, xy.data_ptr(), n, flags, top_item.data_ptr(), n_hit.data_ptr() if n_hit is not None else None, s),
+                   "pm_hit_test_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def item_paths(self) -> np.ndarray:
+        """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
+        n = C.c_uint32(0)
+        st = self._lib.pm_item_paths(self._h, None, 0, C.byref(n))
+        if st not in (_lib.PM_OK, _lib.PM_ERR_CAPACITY):
+            _lib.check(st, "pm_item_paths")
+        out = np.empty(n.value, np.uint32)
+        _lib.check(self._lib.pm_item_paths(self._h, out.ctypes.data, out.size, C.byref(n)), "pm_item_paths")
+        return out
+
     def scene_timings(self) -> dict:
         """Host wall-clock cost of the last scene replacement (flatten+encode, index, arena)."""
         t = _lib.SceneTimings()
