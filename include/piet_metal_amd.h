@@ -124,6 +124,34 @@ typedef struct {
 #define PM_PATH_STROKE 2u
 #define PM_PATH_EVEN_ODD 4u /* fill-rule="evenodd": the fill item gets PM_FILL_EVEN_ODD */
 #define PM_PATH_COMPOUND 8u /* the path's sub-paths become ONE compound Fill item (PM_FILL_COMPOUND): holes work */
+/* Stroke styles (beyond the reference, whose strokes are all round-capped, round-joined distance fields; DESIGN.md 2,
+ * decision D14).  With PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE every sub-path's stroke is encoded as ONE compound non-zero
+ * Fill item -- the stroke's outline, built on the device at the end of the flatten stage -- in the slot of paint order the
+ * poly-line item would have had.  The fields below mean something only together with these two bits; without
+ * PM_PATH_STROKE_OUTLINE they are ignored and the scene is the poly-line scene, byte for byte.
+ *   bits 8-9    cap:  butt 0, round 1, square 2        (3: PM_ERR_INVALID)
+ *   bits 10-11  join: miter 0, round 1, bevel 2        (3: PM_ERR_INVALID)
+ *   bits 16-31  miter limit as an IEEE binary16 value; 0 = 4.0 (SVG's initial value); a value below 1, NaN or
+ *               infinity: PM_ERR_INVALID
+ * A sub-path whose last element is PM_EL_CLOSE is closed: a closing segment, a join at every vertex, no caps. */
+#define PM_PATH_STROKE_OUTLINE 0x10u
+#define PM_STROKE_CAP_BUTT 0u
+#define PM_STROKE_CAP_ROUND 1u
+#define PM_STROKE_CAP_SQUARE 2u
+#define PM_STROKE_JOIN_MITER 0u
+#define PM_STROKE_JOIN_ROUND 1u
+#define PM_STROKE_JOIN_BEVEL 2u
+#define PM_STROKE_CAP_SHIFT 8
+#define PM_STROKE_JOIN_SHIFT 10
+#define PM_STROKE_MITER_SHIFT 16
+/* miter_half = the limit's binary16 bits (0x4400 = 4.0; 0 = the default) */
+#define PM_PATH_STROKE_STYLE(cap, join, miter_half)                                                            \
+    (PM_PATH_STROKE_OUTLINE | (((uint32_t)(cap) & 3u) << PM_STROKE_CAP_SHIFT) | (((uint32_t)(join) & 3u) << PM_STROKE_JOIN_SHIFT) | \
+     (((uint32_t)(miter_half) & 0xffffu) << PM_STROKE_MITER_SHIFT))
+#define PM_PATH_STROKE_CAP(flags) (((flags) >> PM_STROKE_CAP_SHIFT) & 3u)
+#define PM_PATH_STROKE_JOIN(flags) (((flags) >> PM_STROKE_JOIN_SHIFT) & 3u)
+#define PM_PATH_STROKE_MITER_HALF(flags) (((flags) >> PM_STROKE_MITER_SHIFT) & 0xffffu)
+#define PM_PATH_STROKE_STYLE_MASK 0xffff0f10u /* every bit above */
 
 typedef struct {
     uint32_t el_begin, el_end; /* element range of this <path> */
@@ -139,6 +167,9 @@ typedef struct {
 #define PM_SVG_SPEC_DEFAULTS 2    /* SVG's initial `fill: black`, and the sub-paths of a path are filled TOGETHER
                                      (PM_PATH_COMPOUND: holes); default: make_tiger's rules -- only a fill property
                                      (own or inherited) fills (src/lib.rs:299), every sub-path is its own item (:343) */
+#define PM_SVG_STROKE_STYLES 8    /* read stroke-linecap / stroke-linejoin / stroke-miterlimit (inherited presentation properties;
+                                     initial values butt, miter, 4) and set PM_PATH_STROKE_OUTLINE + the style on every stroked
+                                     path; default: they are ignored and every stroke is the reference's round poly-line */
 
 /* Beyond what make_tiger reads (d / fill / stroke / stroke-width of every <path>), pm_svg_parse
  * understands: <g>/<svg> nesting with inherited presentation properties, `transform`
@@ -208,6 +239,9 @@ int pm_upload_scene(pm_ctx *c, size_t bytes);
  * into the device scene buffer (src/lib.rs:293-327, src/flatten.rs:10-47).
  * affine = kurbo Affine coefficients [a b c d e f]; stroke widths are multiplied
  * by `width_scale` in f32 (src/lib.rs:320).  On return the scene is resident.
+ * Paths with PM_PATH_STROKE_OUTLINE get their strokes as outline Fill items (decision D14); *scene_bytes includes the outlines,
+ * *n_items and pm_item_paths are what they are without the bit.  On PM_ERR_CAPACITY *scene_bytes is the size the scene would
+ * have needed (0: not known).
  * Limits: n_els and n_paths <= 2^26 - 1 (PM_ERR_CAPACITY beyond). */
 int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths,
                           const pm_path_el *els, size_t n_els, const double affine[6],

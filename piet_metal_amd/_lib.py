@@ -27,11 +27,18 @@ PM_ERR_PARSE = -6
 
 PM_EL_MOVE, PM_EL_LINE, PM_EL_QUAD, PM_EL_CURVE, PM_EL_CLOSE = range(5)
 PM_PATH_FILL, PM_PATH_STROKE, PM_PATH_EVEN_ODD, PM_PATH_COMPOUND = 1, 2, 4, 8
+# stroke styles (decision D14): with PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE the stroke is an outline Fill item
+PM_PATH_STROKE_OUTLINE = 0x10
+PM_STROKE_CAP_BUTT, PM_STROKE_CAP_ROUND, PM_STROKE_CAP_SQUARE = 0, 1, 2
+PM_STROKE_JOIN_MITER, PM_STROKE_JOIN_ROUND, PM_STROKE_JOIN_BEVEL = 0, 1, 2
+PM_STROKE_CAP_SHIFT, PM_STROKE_JOIN_SHIFT, PM_STROKE_MITER_SHIFT = 8, 10, 16
+PM_PATH_STROKE_STYLE_MASK = 0xFFFF0F10
 PM_FILL_EVEN_ODD = 1
 PM_FILL_COMPOUND = 2
 PM_SVG_REJECT_ARC_PATHS = 1
 PM_SVG_SPEC_DEFAULTS = 2
 PM_SVG_FLAT_GRADIENTS = 4
+PM_SVG_STROKE_STYLES = 8
 PM_FMT_RGBA8, PM_FMT_BGRA8 = 0, 1
 PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1

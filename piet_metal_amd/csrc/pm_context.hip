@@ -2075,6 +2075,7 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
     if (r == PM_ERR_HIP) return HipFail(he, "flatten kernels");
     if (r != PM_OK) {
         if (r != PM_ERR_CAPACITY || g_last_error.empty()) SetError("flatten/encode rejected the paths");
+        if (r == PM_ERR_CAPACITY && scene_bytes) *scene_bytes = bytes;  // the size the scene would have needed (0: not known)
         return r;
     }
     std::swap(c->d_scene, c->d_scene_alt);

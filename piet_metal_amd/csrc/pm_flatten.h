@@ -26,6 +26,7 @@ struct FlattenCache {
     uint8_t *h_meta = nullptr;
     size_t cap_meta = 0, meta_bytes = 0;  // meta_bytes: valid bytes at h_meta + 32 (0: not fetched)
     bool resident = false;
+    bool has_outline = false;  // some resident path asks for PM_PATH_STROKE_OUTLINE: the outline stage runs (pm_stroke_outline.h)
     void Free();
     hipError_t Reserve(size_t n_paths, size_t n_els);  // room for this many paths / elements (pm_create)
 };

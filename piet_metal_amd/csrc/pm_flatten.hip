@@ -15,6 +15,8 @@
 //   K_items   one thread per sub-path: unions the element boxes, writes the
 //             ShortBbox + PietFill / PietStrokePolyLine records (thin-line rule
 //             of src/lib.rs:353-362 included)
+//   K_outline (only when a path asks for PM_PATH_STROKE_OUTLINE; pm_stroke_outline.h, decision D14) a count, a scan and one
+//             wave per styled stroke: the stroke's outline as a compound Fill item in the poly-line's place
 // f64 arithmetic is kept (gfx950 has full-rate f64 FMA pipes; 2k cubics is
 // nothing) so that the bytes match the CPU path exactly.  -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -261,6 +263,13 @@ static uint32_t ScanSplit() {  // (read per scene, not cached: a flatten is not 
     return e && *e ? static_cast<uint32_t>(strtoul(e, nullptr, 10)) : kScanSplit;
 }
 
+// (PM_FLATTEN_SCENE_CAP=<bytes> caps the scene the flatten stage may write, however large the buffer is: the tests reach the
+//  PM_ERR_CAPACITY answer and its needed size with small scenes through it)
+static size_t SceneCapLimit() {
+    const char *e = getenv("PM_FLATTEN_SCENE_CAP");
+    return e && *e ? static_cast<size_t>(strtoull(e, nullptr, 10)) : ~static_cast<size_t>(0);
+}
+
 __global__ __launch_bounds__(kScanThreads) void KScanA(uint32_t n_els, const uint32_t *el_npts, const uint32_t *el_move, uint32_t *el_ptoff,
                                                        uint32_t *el_mvoff, uint32_t *tops) {
     __shared__ uint32_t s_w[kScanThreads / 64];
@@ -363,13 +372,15 @@ __global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_els) return;
     const uint32_t n_items = totals[0];
-    if (Overfull(n_items, *n_pts64, scene_cap)) return;
     const uint32_t n = el_npts[i];
+    const uint32_t tag = els[i].tag;
+    // (written for a scene that does not fit too: the outline stage counts what it would add from it, so that the
+    //  PM_ERR_CAPACITY answer is the whole need at once)
+    if (n != 0 && tag == PM_EL_MOVE) sub_first_el[el_mvoff[i]] = i;
+    if (Overfull(n_items, *n_pts64, scene_cap)) return;
     if (n == 0) return;
     const uint32_t p = PathOf(paths, n_paths, i);
     const pm_path path = paths[p];
-    const uint32_t tag = els[i].tag;
-    if (tag == PM_EL_MOVE) sub_first_el[el_mvoff[i]] = i;
     if (!(path.flags & (PM_PATH_FILL | PM_PATH_STROKE))) return;  // (nothing of it is encoded: its counts are not bounded by scene_cap)
     const uint32_t path_pts = el_ptoff[path.el_end] - el_ptoff[path.el_begin];
     const uint32_t local = el_ptoff[i] - el_ptoff[path.el_begin];
@@ -422,6 +433,16 @@ __global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el
     el_bbox[4 * static_cast<size_t>(i) + 1] = by0;
     el_bbox[4 * static_cast<size_t>(i) + 2] = bx1;
     el_bbox[4 * static_cast<size_t>(i) + 3] = by1;
+}
+
+// The thin-line rule of encode_path_stroke, src/lib.rs:353-362: a stroke narrower than kThinLine is drawn that wide and fainter.
+__device__ __forceinline__ void ThinLine(float *width, uint32_t *rgba) {
+    if (*width < kThinLine) {
+        float alpha = static_cast<float>(*rgba & 0xffu);
+        alpha = alpha * sqrtf(*width / kThinLine);
+        *rgba = (*rgba & ~0xffu) | static_cast<uint32_t>(alpha);
+        *width = kThinLine;
+    }
 }
 
 __device__ __forceinline__ uint16_t SatU16(double v) { return static_cast<uint16_t>(fmin(fmax(v, 0.0), 65535.0)); }
@@ -533,12 +554,7 @@ __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el 
         // encode_path_stroke + Encoder::polyline, src/lib.rs:353-367, :209-222
         float width = path.stroke_width * width_scale;  // src/lib.rs:320
         uint32_t rgba = path.stroke_rgba;
-        if (width < kThinLine) {
-            float alpha = static_cast<float>(rgba & 0xffu);
-            alpha = alpha * sqrtf(width / kThinLine);
-            rgba = (rgba & ~0xffu) | static_cast<uint32_t>(alpha);
-            width = kThinLine;
-        }
+        ThinLine(&width, &rgba);
         if (items_start + (static_cast<size_t>(item) + 1) * kItemSize <= scene_cap) {
             const double hw = static_cast<double>(width * 0.5f);
             ShortBbox sb{SatU16(floor(bx0 - hw)), SatU16(floor(by0 - hw)), SatU16(ceil(bx1 + hw)), SatU16(ceil(by1 + hw))};
@@ -553,6 +569,8 @@ __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el 
         }
     }
 }
+
+#include "pm_stroke_outline.h"
 
 __global__ void KHeader(uint8_t *scene, const uint32_t *totals, uint32_t fixed_n_items, uint32_t scene_cap) {
     // Encoder::begin_group, src/lib.rs:132-144
@@ -595,8 +613,16 @@ hipError_t Grow(T **p, size_t *cap, size_t need) {
 }
 }  // namespace
 
+// d_u32: el_npts, el_move, el_ptoff(+1), el_mvoff(+1), path_item_base, path_pt_base, sub_first, totals / error / 64-bit point sum (16),
+// the parallel scan's block totals (two words per block of 1 024 elements / paths); then, for the outline stage, {total, plain point
+// count} in 64 bits (4 words + 2 of alignment), out_cnt and out_off per sub-path (sub-paths <= elements)
+static size_t ScratchWords(size_t n_paths, size_t n_els) {
+    return n_els * 2 + (n_els + 1) * 2 + n_paths * 2 + n_els + 16 + 2 * ((n_els + 1023) / 1024 + (n_paths + 1023) / 1024);
+}
+static size_t OutlineScratchWords(size_t n_els) { return 6 + 2 * n_els + 1; }
+
 hipError_t FlattenCache::Reserve(size_t n_paths, size_t n_els) {
-    const size_t n_u32 = n_els * 2 + (n_els + 1) * 2 + n_paths * 2 + n_els + 16 + 2 * ((n_els + 1023) / 1024 + (n_paths + 1023) / 1024);
+    const size_t n_u32 = ScratchWords(n_paths, n_els) + OutlineScratchWords(n_els);
     hipError_t e = Grow(&d_paths, &cap_paths, n_paths);
     if (e == hipSuccess) e = Grow(&d_els, &cap_els, n_els);
     if (e == hipSuccess) e = Grow(&d_u32, &cap_u32, n_u32);
@@ -614,6 +640,7 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
                           size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error) {
     hipError_t hip_err = hipSuccess;
     int status = PM_OK;
+    scene_cap = std::min(scene_cap, SceneCapLimit());
     if (use_resident) {
         if (!cache->resident) return PM_ERR_INVALID;
         n_paths = cache->n_paths;
@@ -629,9 +656,7 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
     Affine aff;
     for (int k = 0; k < 6; ++k) aff.m[k] = affine[k];
     const uint32_t ne = static_cast<uint32_t>(n_els), np = static_cast<uint32_t>(n_paths);
-    // (+ the parallel scan's block totals: two words per block of 1 024 elements / paths)
-    const size_t n_u32 = static_cast<size_t>(ne) * 2 + (static_cast<size_t>(ne) + 1) * 2 + static_cast<size_t>(np) * 2 + ne + 16 +
-                         2 * ((static_cast<size_t>(ne) + 1023) / 1024 + (static_cast<size_t>(np) + 1023) / 1024);
+    const size_t n_u32_plain = ScratchWords(np, ne), n_u32 = n_u32_plain + OutlineScratchWords(ne);
 
     // host-side structural check: paths must tile the element array in order
     if (!use_resident) {
@@ -642,6 +667,13 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         }
         if (expect != ne) return PM_ERR_INVALID;
         cache->resident = false;
+        cache->has_outline = false;
+        for (size_t p = 0; p < n_paths; ++p) {
+            const uint32_t fl = h_paths[p].flags;
+            if ((fl & (PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE)) != (PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE)) continue;
+            if (!StrokeStyleValid(fl)) return PM_ERR_INVALID;  // a reserved cap / join code, a miter limit below 1 or not finite
+            cache->has_outline = true;
+        }
     }
     if (n_paths == 0 || n_els == 0) {
         // empty group
@@ -729,6 +761,22 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         hipLaunchKernelGGL(KItems, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_npts, el_ptoff,
                            el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals),
                            static_cast<const unsigned long long *>(d_pts64), d_scene, cap32);
+        if (cache->has_outline) {
+            // Styled strokes (decision D14): their poly-line items become outline Fill items, the outlines behind the end of the
+            // scene as it stands.  KOutlineScan adds their entries to the 64-bit point sum: the host below sizes the scene by it.
+            unsigned long long *d_out64 = reinterpret_cast<unsigned long long *>((reinterpret_cast<uintptr_t>(d_u32 + n_u32_plain) + 7u) & ~static_cast<uintptr_t>(7u));
+            uint32_t *out_cnt = d_u32 + n_u32_plain + 6;
+            uint32_t *out_off = out_cnt + ne;
+            PM_HIP_TRY(hipMemsetAsync(d_out64, 0, 2 * sizeof(unsigned long long), stream));
+            hipLaunchKernelGGL(KOutlineCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), out_cnt, d_out64);
+            hipLaunchKernelGGL(KOutlineScan, dim3(1), dim3(kScanThreads), 0, stream, static_cast<const uint32_t *>(d_totals),
+                               static_cast<const uint32_t *>(out_cnt), out_off, d_out64, d_pts64);
+            hipLaunchKernelGGL(KOutline, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                               static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_off),
+                               static_cast<const unsigned long long *>(d_out64), d_scene, cap32);
+        }
         PM_HIP_TRY(hipGetLastError());
         PM_HIP_TRY(hipMemcpyAsync(h_totals, d_totals, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, stream));
         PM_HIP_TRY(hipMemcpyAsync(cache->h_meta + 32, d_scene, meta_want, hipMemcpyDeviceToHost, stream));

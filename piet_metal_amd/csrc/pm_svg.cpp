@@ -403,7 +403,8 @@ uint32_t ParseColor(const char *s, size_t len) {  // parse_color, src/lib.rs:375
 // Not understood (ignored): patterns and -- unless PM_SVG_FLAT_GRADIENTS turns them into their mean
 // colour -- gradients (painted as if `none`), clipping, masks,
 // text, CSS selectors beyond element / .class / #id, units other than user units / px, stroke
-// joins / caps / dashes.
+// dashes.  stroke-linecap / stroke-linejoin / stroke-miterlimit are read with PM_SVG_STROKE_STYLES (the
+// stroke then is an outline Fill, decision D14); without the flag they are ignored.
 
 struct Affine {  // x' = a x + c y + e, y' = b x + d y + f (the SVG matrix(a b c d e f))
     double a = 1, b = 0, c = 0, d = 1, e = 0, f = 0;
@@ -426,6 +427,8 @@ struct Paint {
 struct Style {
     Paint fill, stroke;
     float stroke_width = 1.0f;
+    uint32_t cap = PM_STROKE_CAP_BUTT, join = PM_STROKE_JOIN_MITER;  // SVG's initial values (read only with PM_SVG_STROKE_STYLES)
+    uint32_t miter_half = 0x4400;                                    // stroke-miterlimit as binary16: 4
     double fill_server_alpha = 1.0, stroke_server_alpha = 1.0;  // mean stop-opacity of a flattened gradient paint
     double opacity = 1.0, fill_opacity = 1.0, stroke_opacity = 1.0;  // opacity: product of the ancestors'
     bool even_odd = false;
@@ -665,6 +668,20 @@ double ParseLength(const Attr *a, double dflt = 0.0, double ref = 0.0) {
     return LengthFromString(std::string(a->val, a->val_len), dflt, ref);
 }
 
+// A number >= 1 as IEEE binary16 bits, rounded to nearest (ties to even), at most 65504: how pm_path.flags carries a miter limit.
+uint32_t HalfBits(double v) {
+    if (!(v < 65504.0)) return 0x7bffu;
+    int e = 0;
+    const double f = std::frexp(v, &e);               // v = f * 2^e, f in [0.5, 1)
+    const double scaled = std::nearbyint(f * 2048.0);  // 11 significant bits (default rounding mode: to nearest even)
+    uint32_t mant = static_cast<uint32_t>(scaled);
+    if (mant == 2048u) {
+        mant = 1024u;
+        ++e;
+    }
+    return (static_cast<uint32_t>(e - 1 + 15) << 10) | (mant - 1024u);
+}
+
 // One presentation property, from an attribute or a `style` declaration (which wins, CSS cascade).
 void ApplyProperty(const std::string &name, const std::string &value, Style *st) {
     if (name == "fill") {
@@ -680,6 +697,18 @@ void ApplyProperty(const std::string &name, const std::string &value, Style *st)
         const float plain = std::strtof(value.c_str(), &rest);
         while (rest && *rest && std::isspace(static_cast<unsigned char>(*rest))) ++rest;
         st->stroke_width = (rest && *rest) ? static_cast<float>(LengthFromString(value, 0.0, 0.0)) : plain;
+    } else if (name == "stroke-linecap") {
+        if (value == "butt") st->cap = PM_STROKE_CAP_BUTT;
+        else if (value == "round") st->cap = PM_STROKE_CAP_ROUND;
+        else if (value == "square") st->cap = PM_STROKE_CAP_SQUARE;
+    } else if (name == "stroke-linejoin") {
+        if (value == "miter") st->join = PM_STROKE_JOIN_MITER;
+        else if (value == "round") st->join = PM_STROKE_JOIN_ROUND;
+        else if (value == "bevel") st->join = PM_STROKE_JOIN_BEVEL;  // (miter-clip / arcs: not understood, the value stays)
+    } else if (name == "stroke-miterlimit") {
+        char *rest = nullptr;
+        const double m = std::strtod(value.c_str(), &rest);
+        if (rest != value.c_str() && m >= 1.0) st->miter_half = HalfBits(m);  // (a limit below 1 is an error in SVG: ignored)
     } else if (name == "fill-rule") {
         if (value == "evenodd") st->even_odd = true;
         else if (value == "nonzero") st->even_odd = false;
@@ -760,7 +789,8 @@ void ParseStyleSheet(const char *p, const char *end, std::vector<CssRule> *rules
 
 bool ApplyElementStyle(const std::vector<Attr> &attrs, Style *st, const std::vector<CssRule> *css = nullptr, const char *el_name = nullptr,
                        size_t el_name_len = 0) {
-    static const char *kProps[] = {"fill", "stroke", "stroke-width", "fill-rule", "fill-opacity", "stroke-opacity", "display", "visibility"};
+    static const char *kProps[] = {"fill", "stroke", "stroke-width", "fill-rule", "fill-opacity", "stroke-opacity", "display", "visibility",
+                                   "stroke-linecap", "stroke-linejoin", "stroke-miterlimit"};
     for (const char *pn : kProps)
         if (const Attr *a = Find(attrs, pn)) ApplyProperty(pn, Trim(a->val, a->val_len), st);
     double opacity_factor = 1.0;  // not inherited: the element's own value multiplies the ancestors'
@@ -1244,6 +1274,7 @@ int ParseRange(Doc *doc, const char *text, const char *end, const Style &initial
                         // widths scale with the geometric mean of the matrix's stretch (exact for similarities)
                         const double det = std::fabs(st.ctm.a * st.ctm.d - st.ctm.b * st.ctm.c);
                         path.stroke_width = st.ctm.IsIdentity() ? st.stroke_width : static_cast<float>(st.stroke_width * std::sqrt(det));
+                        if (flags & PM_SVG_STROKE_STYLES) path.flags |= PM_PATH_STROKE_STYLE(st.cap, st.join, st.miter_half);
                     }
                     if (path.flags & (PM_PATH_FILL | PM_PATH_STROKE)) out->paths.push_back(path);
                     else out->els.resize(el0);

@@ -188,15 +188,19 @@ class PathSet:
         return (s, 0.0, 0.0, s, (width - s * vb[2]) / 2.0 - s * vb[0], (height - s * vb[3]) / 2.0 - s * vb[1]), s
 
     @classmethod
-    def from_svg(cls, text: bytes | str, reject_arc_paths: bool = False, spec_defaults: bool = False, flat_gradients: bool = False) -> "PathSet":
+    def from_svg(cls, text: bytes | str, reject_arc_paths: bool = False, spec_defaults: bool = False, flat_gradients: bool = False,
+                 stroke_styles: bool = False) -> "PathSet":
         """Parse an SVG document.  spec_defaults: SVG's initial `fill: black` instead of the
         reference's rule that only a fill property fills (src/lib.rs:299); flat_gradients: a
-        url(#gradient) paint becomes the mean colour of the gradient's stops instead of `none`."""
+        url(#gradient) paint becomes the mean colour of the gradient's stops instead of `none`;
+        stroke_styles: stroke-linecap / stroke-linejoin / stroke-miterlimit are read and every stroke
+        is drawn as its outline (decision D14) instead of the round poly-line."""
         lib = _lib.load()
         data = text.encode() if isinstance(text, str) else bytes(text)
         err = C.c_int(0)
         flags = (_lib.PM_SVG_REJECT_ARC_PATHS if reject_arc_paths else 0) | (_lib.PM_SVG_SPEC_DEFAULTS if spec_defaults else 0)
         flags |= _lib.PM_SVG_FLAT_GRADIENTS if flat_gradients else 0
+        flags |= _lib.PM_SVG_STROKE_STYLES if stroke_styles else 0
         h = lib.pm_svg_parse(data, len(data), flags, C.byref(err))
         if not h:
             raise _lib.PietMetalError(err.value, "pm_svg_parse")
@@ -211,6 +215,29 @@ class PathSet:
         if not h:
             raise _lib.PietMetalError(err.value, "pm_svg_tiger")
         return cls._from_handle(lib, h)
+
+    CAPS = {"butt": _lib.PM_STROKE_CAP_BUTT, "round": _lib.PM_STROKE_CAP_ROUND, "square": _lib.PM_STROKE_CAP_SQUARE}
+    JOINS = {"miter": _lib.PM_STROKE_JOIN_MITER, "round": _lib.PM_STROKE_JOIN_ROUND, "bevel": _lib.PM_STROKE_JOIN_BEVEL}
+
+    def with_stroke_style(self, cap="butt", join="miter", miter_limit: float = 4.0, select=None) -> "PathSet":
+        """A copy whose stroked paths (all of them, or those of `select`: indices or a boolean mask) are drawn as outlines with
+        this cap ("butt" / "round" / "square"), join ("miter" / "round" / "bevel") and miter limit (kept as binary16; >= 1):
+        PM_PATH_STROKE_OUTLINE and the style fields of pm_path.flags.  Paths without a stroke are left alone."""
+        half = int(np.array(miter_limit, np.float16).view(np.uint16))
+        if not (np.float16(miter_limit) >= 1 and np.isfinite(np.float16(miter_limit))):
+            raise ValueError("miter_limit must be a finite number >= 1")
+        style = (_lib.PM_PATH_STROKE_OUTLINE | (self.CAPS[cap] << _lib.PM_STROKE_CAP_SHIFT) | (self.JOINS[join] << _lib.PM_STROKE_JOIN_SHIFT)
+                 | (half << _lib.PM_STROKE_MITER_SHIFT))
+        p = self.paths.copy()
+        chosen = np.zeros(len(p), bool)
+        chosen[slice(None) if select is None else select] = True
+        chosen &= (p["flags"] & _lib.PM_PATH_STROKE) != 0
+        p["flags"][chosen] = (p["flags"][chosen] & ~np.uint32(_lib.PM_PATH_STROKE_STYLE_MASK)) | np.uint32(style)
+        out = PathSet(p, self.els)
+        for k in ("viewbox", "size"):
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
+        return out
 
     def fills_only(self) -> "PathSet":
         p = self.paths.copy()
