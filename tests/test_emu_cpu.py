@@ -95,3 +95,13 @@ def test_frame_sequences_under_emulation(built):
     out = _run("frame_sequence and (row_lists or split2 or overflow or pairwise00 or pairwise03)",
                test_file="test_frame_sequences.py")
     assert " passed" in out and "failed" not in out
+
+
+def test_edge_scenes_under_emulation(built):
+    """tests/test_edge_scenes.py: the grammar of degenerate and grid-aligned scenes over rows of frame-path switches, through hit
+    testing and as styled strokes, the sweeps of the pixel arithmetic (the blend sweep thinned out) and parity at the coordinate
+    bound -- at the default device and on two CUs.  What the sweeps are for, the MI355X's own arithmetic, only the -m gpu run shows."""
+    out = _run("edge_scenes", workers="8", test_file="test_edge_scenes.py")
+    assert " passed" in out and "failed" not in out
+    out = _run("edge_scenes", {"PM_EMU_CUS": "2"}, workers="8", test_file="test_edge_scenes.py")
+    assert " passed" in out and "failed" not in out
