@@ -161,6 +161,14 @@ typedef struct {
     float stroke_width;        /* user units (NOT yet scaled) */
 } pm_path;                     /* 24 bytes */
 
+/* A dash pattern for one path (decision D15): values [first, first + count) of the call's dash_values, alternately
+ * dash and gap lengths in user units (scaled by width_scale like stroke widths; an odd count is repeated once), 1 <= count <= 32,
+ * every value finite and >= 0; offset: where in the pattern the stroke starts (finite, may be negative). */
+typedef struct {
+    uint32_t path, first, count;
+    float offset;
+} pm_path_dash;                /* 16 bytes */
+
 #define PM_SVG_REJECT_ARC_PATHS 1 /* drop any path whose data holds A/a */
 #define PM_SVG_FLAT_GRADIENTS 4   /* url(#gradient) paints become ONE colour, the mean of the gradient's stops (the renderer has
                                      no gradients; default: such a paint is `none`, the element is not drawn with it) */
@@ -170,6 +178,9 @@ typedef struct {
 #define PM_SVG_STROKE_STYLES 8    /* read stroke-linecap / stroke-linejoin / stroke-miterlimit (inherited presentation properties;
                                      initial values butt, miter, 4) and set PM_PATH_STROKE_OUTLINE + the style on every stroked
                                      path; default: they are ignored and every stroke is the reference's round poly-line */
+#define PM_SVG_STROKE_DASHES 16   /* needs PM_SVG_STROKE_STYLES (PM_ERR_INVALID without): read stroke-dasharray / stroke-dashoffset
+                                     (inherited; none, comma or space lists of lengths, a negative entry means none) into the dash
+                                     table pm_svg_dashes / pm_svg_dash_values, scaled by sqrt|det| like widths */
 
 /* Beyond what make_tiger reads (d / fill / stroke / stroke-width of every <path>), pm_svg_parse
  * understands: <g>/<svg> nesting with inherited presentation properties, `transform`
@@ -203,6 +214,11 @@ size_t pm_svg_n_els(const pm_svg *s);
 int pm_svg_viewbox(const pm_svg *s, double viewbox[4], double *width, double *height);
 const pm_path *pm_svg_paths(const pm_svg *s);
 const pm_path_el *pm_svg_els(const pm_svg *s);
+/* The dash table of the parse (empty without PM_SVG_STROKE_DASHES), as pm_flatten_and_encode_dashed takes it. */
+const pm_path_dash *pm_svg_dashes(const pm_svg *s);
+size_t pm_svg_n_dashes(const pm_svg *s);
+const float *pm_svg_dash_values(const pm_svg *s);
+size_t pm_svg_n_dash_values(const pm_svg *s);
 uint32_t pm_parse_color(const char *s); /* parse_color src/lib.rs:375-385 */
 
 /* ==== 3. renderer (replaces PietRenderer, TestApp/PietRenderer.{h,m}) ========= */
@@ -251,6 +267,17 @@ int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths,
  * re-encodes on the CPU when the view changes (PietRenderer.m:90-101, :145); here a view change
  * is four small kernels plus the scene index. */
 int pm_reflatten(pm_ctx *c, const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
+/* pm_flatten_and_encode with a dash table (decision D15): the styled stroke of every path named in `dashes` is cut into dashes
+ * on the device.  A dashed stroke stays ONE compound Fill item per sub-path in the poly-line's slot -- *n_items and pm_item_paths
+ * do not change -- whose entries are the D14 outlines of its dashes.  `dashes` is strictly ascending by path; PM_ERR_INVALID: an
+ * index >= n_paths, a path without PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE, a count of 0 or above 32, a range outside dash_values,
+ * a negative or non-finite value, a non-finite offset.  With n_dashes == 0 it is pm_flatten_and_encode.  The table stays resident
+ * with the paths: pm_reflatten cuts again under its width_scale; a later pm_flatten_and_encode forgets it.
+ * Limits: a segment or a pattern value longer than 65 536 px counts as 65 536 px; on PM_ERR_CAPACITY *scene_bytes counts the
+ * dashes only if the scene without outlines fitted (else the undashed outlines: the call that follows learns the rest). */
+int pm_flatten_and_encode_dashed(pm_ctx *c, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
+                                 const pm_path_dash *dashes, size_t n_dashes, const float *dash_values, size_t n_dash_values,
+                                 const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
 /* Copy the resident scene back (parity checks, init_test_scene). */
 int pm_download_scene(pm_ctx *c, uint8_t *dst, size_t cap, size_t *bytes);
 

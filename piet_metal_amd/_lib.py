@@ -39,6 +39,7 @@ PM_SVG_REJECT_ARC_PATHS = 1
 PM_SVG_SPEC_DEFAULTS = 2
 PM_SVG_FLAT_GRADIENTS = 4
 PM_SVG_STROKE_STYLES = 8
+PM_SVG_STROKE_DASHES = 16  # needs PM_SVG_STROKE_STYLES
 PM_FMT_RGBA8, PM_FMT_BGRA8 = 0, 1
 PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1
@@ -116,6 +117,10 @@ SIGNATURES = {
     "pm_svg_viewbox": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "pm_svg_paths": (C.POINTER(Path), [C.c_void_p]),
     "pm_svg_els": (C.POINTER(PathEl), [C.c_void_p]),
+    "pm_svg_dashes": (C.c_void_p, [C.c_void_p]),
+    "pm_svg_n_dashes": (C.c_size_t, [C.c_void_p]),
+    "pm_svg_dash_values": (C.c_void_p, [C.c_void_p]),
+    "pm_svg_n_dash_values": (C.c_size_t, [C.c_void_p]),
     "pm_parse_color": (C.c_uint32, [C.c_char_p]),
     "pm_create": (C.c_void_p, [C.c_int, C.POINTER(C.c_int)]),
     "pm_destroy": (None, [C.c_void_p]),
@@ -127,6 +132,8 @@ SIGNATURES = {
     "pm_scene_reserve": (C.c_int, [C.c_void_p, C.c_size_t]),
     "pm_upload_scene": (C.c_int, [C.c_void_p, C.c_size_t]),
     "pm_flatten_and_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "pm_flatten_and_encode_dashed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "pm_reflatten": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "pm_download_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pm_render": (C.c_int, [C.c_void_p]),

@@ -74,6 +74,7 @@ def main(argv=None) -> int:
     ap.add_argument("--reference-fill-rule", action="store_true", help="files: only a fill property fills (make_tiger, src/lib.rs:299) instead of SVG's initial black")
     ap.add_argument("--no-flat-gradients", action="store_true", help="files: do not draw gradient paints at all (default: as the mean colour of their stops)")
     ap.add_argument("--stroke-styles", action="store_true", help="files: read stroke-linecap / stroke-linejoin / stroke-miterlimit and draw strokes as outlines with those caps and joins (default: every stroke is the round poly-line)")
+    ap.add_argument("--stroke-dashes", action="store_true", help="files: also read stroke-dasharray / stroke-dashoffset and cut the outlined strokes into dashes (implies --stroke-styles)")
     ap.add_argument("--frames", type=int, default=1, help="render an animation of this many frames (output NAME-###.png)")
     ap.add_argument("--spin", type=float, default=360.0, help="--frames: total rotation about the viewport centre, degrees")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
@@ -92,7 +93,7 @@ def main(argv=None) -> int:
     else:
         with open(args.input, "rb") as f:
             paths = PathSet.from_svg(f.read(), args.reject_arc_paths, spec_defaults=not args.reference_fill_rule, flat_gradients=not args.no_flat_gradients,
-                                     stroke_styles=args.stroke_styles)
+                                     stroke_styles=args.stroke_styles or args.stroke_dashes, stroke_dashes=args.stroke_dashes)
     scale = args.scale if args.scale is not None else args.height / 200.0
     off = args.offset if args.offset is not None else ((args.width - args.height) / 2.0 if args.scale is None else 0.0, 0.0)
     base = (scale, 0.0, 0.0, scale, float(off[0]), float(off[1]))

@@ -2017,7 +2017,7 @@ int pm_upload_scene(pm_ctx *c, size_t bytes) {
 }
 
 namespace {
-int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
+int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els, const pm::DashTable *dash,
                      const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
 }
 
@@ -2028,11 +2028,24 @@ int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths, const
     c->fb_applied = false;
     c->replan_wide = false;
     c->plan_reusable = false;  // (new paths: planned afresh, for their own boxes)
-    return FlattenAndEncode(c, false, paths, n_paths, els, n_els, affine, width_scale, scene_bytes, n_items);
+    return FlattenAndEncode(c, false, paths, n_paths, els, n_els, nullptr, affine, width_scale, scene_bytes, n_items);
+}
+
+int pm_flatten_and_encode_dashed(pm_ctx *c, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
+                                 const pm_path_dash *dashes, size_t n_dashes, const float *dash_values, size_t n_dash_values,
+                                 const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items) {
+    if (n_dashes == 0) return pm_flatten_and_encode(c, paths, n_paths, els, n_els, affine, width_scale, scene_bytes, n_items);
+    if (!c || !affine || (n_paths && !paths) || (n_els && !els) || !dashes || (n_dash_values && !dash_values)) return PM_ERR_INVALID;
+    c->fb_slots.clear();
+    c->fb_applied = false;
+    c->replan_wide = false;
+    c->plan_reusable = false;
+    const pm::DashTable table{dashes, n_dashes, dash_values, n_dash_values};
+    return FlattenAndEncode(c, false, paths, n_paths, els, n_els, &table, affine, width_scale, scene_bytes, n_items);
 }
 
 namespace {
-int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
+int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els, const pm::DashTable *dash,
                      const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items) {
     PM_TRY(hipSetDevice(c->device));
     size_t bytes = 0;
@@ -2054,14 +2067,15 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
     };
     int r = grow_alt(c->dev_scene_cap);
     if (r == PM_OK)
-        r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, affine, width_scale, c->d_scene_alt,
+        r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, dash, affine, width_scale, c->d_scene_alt,
                                       c->dev_scene_alt_cap, &bytes, &items, &he);
-    if (r == PM_ERR_CAPACITY && bytes > c->dev_scene_alt_cap) {
+    // (a dash table: the dashes of a scene whose poly-lines did not fit are counted by the call after the one that made room for them)
+    for (int attempt = 0; attempt < (c->flatten_cache.n_dashes ? 2 : 1) && r == PM_ERR_CAPACITY && bytes > c->dev_scene_alt_cap; ++attempt) {
         // grow it (the kernels write it; nothing is staged on the host) and retry once.  `bytes` is the exact need (the point count
         // behind it is summed in 64 bits): beyond 4 GiB - 1 grow_alt refuses it; the headroom never makes a need that fits not fit.
         r = grow_alt(std::max<size_t>(bytes, std::min<size_t>(bytes + (bytes >> 3), 0xffffffffull)));
         if (r == PM_OK)
-            r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, affine, width_scale, c->d_scene_alt,
+            r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, dash, affine, width_scale, c->d_scene_alt,
                                           c->dev_scene_alt_cap, &bytes, &items, &he);
     }
     const float flatten_ms = timer.ms();
@@ -2097,7 +2111,7 @@ int pm_reflatten(pm_ctx *c, const double affine[6], float width_scale, size_t *s
         return PM_ERR_INVALID;
     }
     c->replan_wide = true;  // (a view change: the next plan is made to last, EnsureArena)
-    return FlattenAndEncode(c, true, nullptr, 0, nullptr, 0, affine, width_scale, scene_bytes, n_items);
+    return FlattenAndEncode(c, true, nullptr, 0, nullptr, 0, nullptr, affine, width_scale, scene_bytes, n_items);
 }
 
 int pm_download_scene(pm_ctx *c, uint8_t *dst, size_t cap, size_t *bytes) {

@@ -4,6 +4,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 #include "../../include/piet_metal_amd.h"
 
@@ -27,15 +28,29 @@ struct FlattenCache {
     size_t cap_meta = 0, meta_bytes = 0;  // meta_bytes: valid bytes at h_meta + 32 (0: not fetched)
     bool resident = false;
     bool has_outline = false;  // some resident path asks for PM_PATH_STROKE_OUTLINE: the outline stage runs (pm_stroke_outline.h)
+    // the dash table of the resident paths (decision D15, pm_dash.h): n_dashes records of four words, a word per path (its
+    // record's index or ~0), the values; n_dashes == 0: no table, the dash kernels are not launched
+    uint32_t *d_dash = nullptr;
+    size_t cap_dash = 0, n_dashes = 0;
+    std::vector<uint32_t> h_dash;  // (the staging copy the upload reads)
     void Free();
     hipError_t Reserve(size_t n_paths, size_t n_els);  // room for this many paths / elements (pm_create)
 };
 
+// A dash table as pm_flatten_and_encode_dashed takes it (checked by FlattenEncodeOnDevice).
+struct DashTable {
+    const pm_path_dash *dashes;
+    size_t n_dashes;
+    const float *values;
+    size_t n_values;
+};
+
 // Flatten + encode on the device (see pm_flatten.hip).  Synchronises `stream` (once, at the end).
+// dash: nullptr or the paths' dash table (ignored with use_resident: the resident one is used again).
 // use_resident: ignore h_paths / h_els and flatten the paths resident in `cache` again.
 // On PM_ERR_CAPACITY *scene_bytes holds the size that would have been needed.
 int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resident, const pm_path *h_paths, size_t n_paths, const pm_path_el *h_els,
-                          size_t n_els, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
+                          size_t n_els, const DashTable *dash, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
                           size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error);
 
 // First item of every resident path in the scene the kernels last wrote (h_base: cache->n_paths entries; path p's items are

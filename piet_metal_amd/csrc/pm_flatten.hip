@@ -17,11 +17,14 @@
 //             of src/lib.rs:353-362 included)
 //   K_outline (only when a path asks for PM_PATH_STROKE_OUTLINE; pm_stroke_outline.h, decision D14) a count, a scan and one
 //             wave per styled stroke: the stroke's outline as a compound Fill item in the poly-line's place
+//   K_dash    (only with a dash table, pm_flatten_and_encode_dashed; pm_dash.h, decision D15) a count and one wave per dashed
+//             stroke: the outlines of its dashes, one after another, as that one item's entries
 // f64 arithmetic is kept (gfx950 has full-rate f64 FMA pipes; 2k cubics is
 // nothing) so that the bytes match the CPU path exactly.  -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <cstring>
 
@@ -167,6 +170,7 @@ __global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el 
 // One workgroup.  Exclusive scans with totals at index n.
 constexpr int kScanThreads = 1024;
 constexpr size_t kMaxFlattenEls = (1u << 26) - 1u;  // elements / paths of one pm_flatten_and_encode call
+constexpr uint32_t kMaxDashValues = 32;              // values of one dash pattern
 
 __device__ uint32_t BlockScan1024(uint32_t v, uint32_t *s_w, uint32_t *total) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
@@ -571,6 +575,7 @@ __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el 
 }
 
 #include "pm_stroke_outline.h"
+#include "pm_dash.h"
 
 __global__ void KHeader(uint8_t *scene, const uint32_t *totals, uint32_t fixed_n_items, uint32_t scene_cap) {
     // Encoder::begin_group, src/lib.rs:132-144
@@ -595,6 +600,7 @@ void FlattenCache::Free() {
     if (d_els) (void)hipFree(d_els);
     if (d_u32) (void)hipFree(d_u32);
     if (d_bbox) (void)hipFree(d_bbox);
+    if (d_dash) (void)hipFree(d_dash);
     if (h_meta) (void)hipHostFree(h_meta);
     *this = FlattenCache();
 }
@@ -636,7 +642,7 @@ hipError_t FlattenCache::Reserve(size_t n_paths, size_t n_els) {
 
 
 int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resident, const pm_path *h_paths, size_t n_paths, const pm_path_el *h_els,
-                          size_t n_els, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
+                          size_t n_els, const DashTable *dash, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
                           size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error) {
     hipError_t hip_err = hipSuccess;
     int status = PM_OK;
@@ -674,6 +680,21 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
             if (!StrokeStyleValid(fl)) return PM_ERR_INVALID;  // a reserved cap / join code, a miter limit below 1 or not finite
             cache->has_outline = true;
         }
+        // the dash table (decision D15): strictly ascending by path, on stroked, outlined paths, 1 .. 32 finite values >= 0 each
+        cache->n_dashes = 0;
+        const size_t nd = dash ? dash->n_dashes : 0;
+        for (size_t i = 0; i < nd; ++i) {
+            const pm_path_dash &d = dash->dashes[i];
+            if (d.path >= n_paths || (i > 0 && d.path <= dash->dashes[i - 1].path)) return PM_ERR_INVALID;
+            if ((h_paths[d.path].flags & (PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE)) != (PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE)) return PM_ERR_INVALID;
+            if (d.count == 0 || d.count > kMaxDashValues || d.first > dash->n_values || d.count > dash->n_values - d.first) return PM_ERR_INVALID;
+            if (!std::isfinite(d.offset)) return PM_ERR_INVALID;
+            for (uint32_t j = 0; j < d.count; ++j) {
+                const float v = dash->values[d.first + j];
+                if (!(std::isfinite(v) && v >= 0.0f)) return PM_ERR_INVALID;
+            }
+        }
+        if (nd != 0 && (n_paths == 0 || n_els == 0)) return PM_ERR_INVALID;  // (not reached: an index >= n_paths above)
     }
     if (n_paths == 0 || n_els == 0) {
         // empty group
@@ -705,6 +726,17 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         size_t moves = 0;
         for (size_t i = 0; i < n_els; ++i) moves += h_els[i].tag == PM_EL_MOVE ? 1u : 0u;
         cache->max_items = 2 * moves + n_paths;
+        if (dash && dash->n_dashes) {
+            // resident beside the paths: the records, path -> record (kNoDash: none), the values -- one allocation of words
+            const size_t nd = dash->n_dashes, words = 4 * nd + n_paths + dash->n_values;
+            PM_HIP_TRY(Grow(&cache->d_dash, &cache->cap_dash, words));
+            cache->h_dash.assign(words, kNoDash);
+            std::memcpy(cache->h_dash.data(), dash->dashes, nd * sizeof(pm_path_dash));
+            for (size_t i = 0; i < nd; ++i) cache->h_dash[4 * nd + dash->dashes[i].path] = static_cast<uint32_t>(i);
+            std::memcpy(cache->h_dash.data() + 4 * nd + n_paths, dash->values, dash->n_values * sizeof(float));
+            PM_HIP_TRY(hipMemcpyAsync(cache->d_dash, cache->h_dash.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+            cache->n_dashes = nd;
+        }
     }
     {
         // The four kernels go out back to back: what KPoints / KItems need from KScan (item count, sub-path
@@ -767,15 +799,32 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
             unsigned long long *d_out64 = reinterpret_cast<unsigned long long *>((reinterpret_cast<uintptr_t>(d_u32 + n_u32_plain) + 7u) & ~static_cast<uintptr_t>(7u));
             uint32_t *out_cnt = d_u32 + n_u32_plain + 6;
             uint32_t *out_off = out_cnt + ne;
+            // Dashed strokes (decision D15, pm_dash.h): their sub-paths are skipped by the two outline kernels and counted / cut by
+            // KDashCount / KDash; a scene without a dash table launches exactly what it did.
+            const bool has_dash = cache->n_dashes != 0;
+            const pm_path_dash *d_dashes = reinterpret_cast<const pm_path_dash *>(cache->d_dash);
+            const uint32_t *path_dash = has_dash ? cache->d_dash + 4 * cache->n_dashes : nullptr;
+            const float *d_dash_values = has_dash ? reinterpret_cast<const float *>(cache->d_dash + 4 * cache->n_dashes + np) : nullptr;
             PM_HIP_TRY(hipMemsetAsync(d_out64, 0, 2 * sizeof(unsigned long long), stream));
             hipLaunchKernelGGL(KOutlineCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
-                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), out_cnt, d_out64);
+                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), path_dash, out_cnt, d_out64);
+            if (has_dash)
+                hipLaunchKernelGGL(KDashCount, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), path_dash, d_dashes, d_dash_values,
+                                   static_cast<const uint8_t *>(d_scene), cap32, out_cnt, d_out64);
             hipLaunchKernelGGL(KOutlineScan, dim3(1), dim3(kScanThreads), 0, stream, static_cast<const uint32_t *>(d_totals),
                                static_cast<const uint32_t *>(out_cnt), out_off, d_out64, d_pts64);
             hipLaunchKernelGGL(KOutline, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
                                path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
                                static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_off),
-                               static_cast<const unsigned long long *>(d_out64), d_scene, cap32);
+                               static_cast<const unsigned long long *>(d_out64), path_dash, d_scene, cap32);
+            if (has_dash)
+                hipLaunchKernelGGL(KDash, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_cnt),
+                                   static_cast<const uint32_t *>(out_off), static_cast<const unsigned long long *>(d_out64), path_dash, d_dashes,
+                                   d_dash_values, d_scene, cap32);
         }
         PM_HIP_TRY(hipGetLastError());
         PM_HIP_TRY(hipMemcpyAsync(h_totals, d_totals, sizeof(uint32_t) * 8, hipMemcpyDeviceToHost, stream));

@@ -41,6 +41,7 @@
 // points at the end of the scene as it is without outlines (items in paint order).  ShortBbox: floor / ceil of the min / max of
 // the stored f32 outline points, saturated to u16 as for fills; no entries: the zero box.
 // A non-finite poly-line point makes the entries it touches NaN (no bit pattern is promised for them).
+// A path with a dash pattern (decision D15, pm_dash.h) is not outlined here: KOutlineCount and KOutline skip its sub-paths.
 #pragma once
 
 // kLevelHw = {0.1, 0.3414, 1.3137, 5.2043, 20.767, 83.018}: 0.1 / (1 - cos(pi / 2^(L+1))) rounded down -- the largest hw whose half
@@ -89,6 +90,7 @@ struct OutlineJob {
     bool closed;
     uint32_t n;       // poly-line points
     uint32_t item;    // the stroke's item
+    uint32_t path;    // its path
     size_t pts_ix;    // byte offset of the poly-line's points
     uint32_t rgba;    // after the thin-line rule
     double hw;
@@ -104,6 +106,7 @@ __device__ __forceinline__ OutlineJob MakeOutlineJob(const pm_path *paths, uint3
     const uint32_t p = PathOf(paths, n_paths, first);
     const pm_path path = paths[p];
     job.styled = IsOutlined(path.flags);
+    job.path = p;
     if (!job.styled) return job;
     // (the stroke's slot, as KItems numbers it: behind the path's fill items and fill points)
     const uint32_t sub0 = el_mvoff[path.el_begin];
@@ -146,16 +149,22 @@ __device__ __forceinline__ OutlineLayout LayoutOf(const OutlineJob &job) {
     return lay;
 }
 
+// no dash table, or none for this path (decision D15, pm_dash.h: a dashed sub-path is KDashCount's and KDash's)
+constexpr uint32_t kNoDash = 0xffffffffu;
+__device__ __forceinline__ bool IsDashed(const uint32_t *path_dash, uint32_t p) { return path_dash != nullptr && path_dash[p] != kNoDash; }
+
 // One thread per sub-path: out_cnt[s] = entries of its outline (0: not a styled stroke); their 64-bit sum to *out_total.
 __global__ void KOutlineCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
                               const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
-                              const uint32_t *sub_first_el, const uint32_t *totals, uint32_t *out_cnt, unsigned long long *out_total) {
+                              const uint32_t *sub_first_el, const uint32_t *totals, const uint32_t *path_dash, uint32_t *out_cnt,
+                              unsigned long long *out_total) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long q = 0;
     if (s < totals[2]) {
         const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals[0], s);
-        if (job.styled) q = LayoutOf(job).total;
-        out_cnt[s] = static_cast<uint32_t>(q);  // (a count past 2^32 never fits: the 64-bit sum says so, KOutline then writes nothing)
+        const bool dashed = job.styled && IsDashed(path_dash, job.path);
+        if (job.styled && !dashed) q = LayoutOf(job).total;
+        if (!dashed) out_cnt[s] = static_cast<uint32_t>(q);  // (a count past 2^32 never fits: the 64-bit sum says so, KOutline then writes nothing)
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d, 64);
@@ -315,24 +324,32 @@ __device__ void EmitCorner(OutlineSink &sink, unsigned long long e, CornerKind k
     sink.Separator(e, first);
 }
 
-// One WAVE per sub-path, as in KItems: the lanes stride over the vertices; a lane writes its vertex's segment, join and cap
-// pieces; the box is reduced over the wave and lane 0 rewrites the item record and its ShortBbox in place.
-__global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
-                         const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
-                         const uint32_t *totals, const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
-                         uint8_t *scene, uint32_t scene_cap) {
-    const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t n_items = totals[0], n_subs = totals[2];
-    if (s >= n_subs || Overfull(n_items, *n_pts64, scene_cap)) return;  // (whole waves; *n_pts64 counts the outlines by now)
-    const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
-    if (!job.styled) return;  // (uniform)
-    const OutlineLayout lay = LayoutOf(job);
-    const size_t bbox_start = sizeof(SimpleGroup);
-    const size_t items_start = bbox_start + static_cast<size_t>(n_items) * sizeof(ShortBbox);
-    const size_t outlines_start = items_start + static_cast<size_t>(n_items) * kItemSize + 8 * static_cast<size_t>(out_total[1]);
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    OutlineSink sink{scene, outlines_start + 8 * static_cast<size_t>(out_off[s]), scene_cap, nan, nan, nan, nan, false};
+// The join at p between the directions d1 (in) and d2 (out), either of which may not exist.
+__device__ __forceinline__ void EmitJoin(OutlineSink &sink, unsigned long long e, CornerKind kind, V2 p, bool has1, V2 d1, bool has2, V2 d2, double hw,
+                                         double mlim, uint32_t L) {
+    const double c = d1.x * d2.y - d1.y * d2.x, dot = d1.x * d2.x + d1.y * d2.y;
+    V2 e0 = p, e1 = p, mid = p;
+    bool half_turn = false, collapse = false;
+    if (has1 && has2 && c > 0.0) {
+        e0 = V2{d1.y, -d1.x};
+        e1 = V2{d2.y, -d2.x};
+    } else if (has1 && has2 && c < 0.0) {
+        e0 = V2{-d2.y, d2.x};
+        e1 = V2{-d1.y, d1.x};
+    } else if (has1 && has2 && c == 0.0 && dot < 0.0) {
+        e0 = V2{d1.y, -d1.x};
+        e1 = V2{-d1.y, d1.x};
+        mid = d1;
+        half_turn = true;
+    } else {
+        collapse = true;
+    }
+    EmitCorner(sink, e, kind, p, e0, e1, mid, half_turn, collapse, dot, hw, mlim, L);
+}
+
+// The D14 outline of one sub-path, by one wave: the lanes stride over the vertices; a lane writes its vertex's segment, join and
+// cap pieces.
+__device__ __forceinline__ void OutlineSubpath(const uint8_t *scene, const OutlineJob &job, const OutlineLayout &lay, OutlineSink &sink, uint32_t lane) {
     const uint32_t n = job.n, nseg = static_cast<uint32_t>(lay.nseg);
     const double hw = job.hw;
     const unsigned long long joins_at = 5ull * lay.nseg, caps_at = joins_at + lay.join_size * lay.njoin;
@@ -360,26 +377,7 @@ __global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n
         if (!joined && !capped) continue;
         V2 d1{0.0, 0.0}, d2{0.0, 0.0};
         const bool has1 = VertexDir(scene, job, nseg, i, true, &d1), has2 = VertexDir(scene, job, nseg, i, false, &d2);
-        if (joined) {
-            const double c = d1.x * d2.y - d1.y * d2.x, dot = d1.x * d2.x + d1.y * d2.y;
-            V2 e0 = p, e1 = p, mid = p;
-            bool half_turn = false, collapse = false;
-            if (has1 && has2 && c > 0.0) {
-                e0 = V2{d1.y, -d1.x};
-                e1 = V2{d2.y, -d2.x};
-            } else if (has1 && has2 && c < 0.0) {
-                e0 = V2{-d2.y, d2.x};
-                e1 = V2{-d1.y, d1.x};
-            } else if (has1 && has2 && c == 0.0 && dot < 0.0) {
-                e0 = V2{d1.y, -d1.x};
-                e1 = V2{-d1.y, d1.x};
-                mid = d1;
-                half_turn = true;
-            } else {
-                collapse = true;
-            }
-            EmitCorner(sink, joins_at + lay.join_size * (job.closed ? i : i - 1u), join_kind, p, e0, e1, mid, half_turn, collapse, dot, hw, job.mlim, job.L);
-        }
+        if (joined) EmitJoin(sink, joins_at + lay.join_size * (job.closed ? i : i - 1u), join_kind, p, has1, d1, has2, d2, hw, job.mlim, job.L);
         if (capped) {
             // (a sub-path of one point is both ends)
             for (uint32_t end = 0; end < 2; ++end) {
@@ -393,6 +391,13 @@ __global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n
             }
         }
     }
+}
+
+// The box is reduced over the wave and lane 0 rewrites the item record and its ShortBbox in place.
+__device__ __forceinline__ void WriteOutlineItem(uint8_t *scene, uint32_t scene_cap, uint32_t n_items, const OutlineJob &job, OutlineSink &sink,
+                                                 uint32_t total, uint32_t lane) {
+    const size_t bbox_start = sizeof(SimpleGroup);
+    const size_t items_start = bbox_start + static_cast<size_t>(n_items) * sizeof(ShortBbox);
     WaveBox(sink.x0, sink.y0, sink.x1, sink.y1);
     if (__ballot(sink.any) == 0ull) sink.x0 = sink.y0 = sink.x1 = sink.y1 = 0.0;
     if (lane == 0 && items_start + (static_cast<size_t>(job.item) + 1) * kItemSize <= scene_cap) {
@@ -402,8 +407,27 @@ __global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n
         it[0] = kItemFill;
         it[1] = kFillCompound;
         it[2] = __builtin_bswap32(job.rgba);
-        it[3] = static_cast<uint32_t>(lay.total);
+        it[3] = total;
         it[4] = static_cast<uint32_t>(sink.at);
         it[5] = it[6] = it[7] = 0;
     }
+}
+
+// One WAVE per sub-path, as in KItems.
+__global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
+                         const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                         const uint32_t *totals, const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
+                         const uint32_t *path_dash, uint8_t *scene, uint32_t scene_cap) {
+    const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t n_items = totals[0], n_subs = totals[2];
+    if (s >= n_subs || Overfull(n_items, *n_pts64, scene_cap)) return;  // (whole waves; *n_pts64 counts the outlines by now)
+    const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
+    if (!job.styled || IsDashed(path_dash, job.path)) return;  // (uniform)
+    const OutlineLayout lay = LayoutOf(job);
+    const size_t outlines_start = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize) + 8 * static_cast<size_t>(out_total[1]);
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    OutlineSink sink{scene, outlines_start + 8 * static_cast<size_t>(out_off[s]), scene_cap, nan, nan, nan, nan, false};
+    OutlineSubpath(scene, job, lay, sink, lane);
+    WriteOutlineItem(scene, scene_cap, n_items, job, sink, static_cast<uint32_t>(lay.total), lane);
 }

@@ -46,6 +46,8 @@ extern "C" const char pm_tiger_svg_end[];
 struct pm_svg {
     std::vector<pm_path> paths;
     std::vector<pm_path_el> els;
+    std::vector<pm_path_dash> dashes;  // with PM_SVG_STROKE_DASHES: the dash table (decision D15), ascending by path
+    std::vector<float> dash_values;
     // the outermost <svg>: viewBox (if any), width / height in user units (0: absent or a percentage)
     bool has_viewbox = false, seen_root = false;
     double viewbox[4] = {0, 0, 0, 0};
@@ -402,9 +404,11 @@ uint32_t ParseColor(const char *s, size_t len) {  // parse_color, src/lib.rs:375
 // <use> draws the element (or <symbol>) its href names, wherever that is defined.
 // Not understood (ignored): patterns and -- unless PM_SVG_FLAT_GRADIENTS turns them into their mean
 // colour -- gradients (painted as if `none`), clipping, masks,
-// text, CSS selectors beyond element / .class / #id, units other than user units / px, stroke
-// dashes.  stroke-linecap / stroke-linejoin / stroke-miterlimit are read with PM_SVG_STROKE_STYLES (the
-// stroke then is an outline Fill, decision D14); without the flag they are ignored.
+// text, CSS selectors beyond element / .class / #id, units other than user units / px.
+// stroke-linecap / stroke-linejoin / stroke-miterlimit are read with PM_SVG_STROKE_STYLES (the
+// stroke then is an outline Fill, decision D14); without the flag they are ignored.  stroke-dasharray /
+// stroke-dashoffset are read with PM_SVG_STROKE_DASHES on top of it (the dash table, decision D15; percentages
+// and lists of more than 32 values are not understood: such a stroke is drawn solid); without it they are ignored.
 
 struct Affine {  // x' = a x + c y + e, y' = b x + d y + f (the SVG matrix(a b c d e f))
     double a = 1, b = 0, c = 0, d = 1, e = 0, f = 0;
@@ -429,6 +433,8 @@ struct Style {
     float stroke_width = 1.0f;
     uint32_t cap = PM_STROKE_CAP_BUTT, join = PM_STROKE_JOIN_MITER;  // SVG's initial values (read only with PM_SVG_STROKE_STYLES)
     uint32_t miter_half = 0x4400;                                    // stroke-miterlimit as binary16: 4
+    std::vector<float> dash;                                         // stroke-dasharray (empty: none), stroke-dashoffset
+    float dash_offset = 0.0f;
     double fill_server_alpha = 1.0, stroke_server_alpha = 1.0;  // mean stop-opacity of a flattened gradient paint
     double opacity = 1.0, fill_opacity = 1.0, stroke_opacity = 1.0;  // opacity: product of the ancestors'
     bool even_odd = false;
@@ -709,6 +715,28 @@ void ApplyProperty(const std::string &name, const std::string &value, Style *st)
         char *rest = nullptr;
         const double m = std::strtod(value.c_str(), &rest);
         if (rest != value.c_str() && m >= 1.0) st->miter_half = HalfBits(m);  // (a limit below 1 is an error in SVG: ignored)
+    } else if (name == "stroke-dasharray") {
+        // none, or a comma / space list of lengths; a negative entry (an error in SVG) means none, and so does a list this
+        // front-end cannot carry (more than 32 values) or read
+        st->dash.clear();
+        if (value != "none") {
+            std::vector<float> list;
+            bool ok = true;
+            for (size_t i = 0; i < value.size() && ok;) {
+                while (i < value.size() && (value[i] == ',' || std::isspace(static_cast<unsigned char>(value[i])))) ++i;
+                if (i >= value.size()) break;
+                size_t j = i;
+                while (j < value.size() && value[j] != ',' && !std::isspace(static_cast<unsigned char>(value[j]))) ++j;
+                const double v = LengthFromString(value.substr(i, j - i), -1.0, 0.0);
+                ok = std::isfinite(v) && v >= 0.0 && list.size() < 32;
+                list.push_back(static_cast<float>(v));
+                i = j;
+            }
+            if (ok) st->dash = list;
+        }
+    } else if (name == "stroke-dashoffset") {
+        const double v = LengthFromString(value, 0.0, 0.0);
+        if (std::isfinite(v)) st->dash_offset = static_cast<float>(v);
     } else if (name == "fill-rule") {
         if (value == "evenodd") st->even_odd = true;
         else if (value == "nonzero") st->even_odd = false;
@@ -790,7 +818,7 @@ void ParseStyleSheet(const char *p, const char *end, std::vector<CssRule> *rules
 bool ApplyElementStyle(const std::vector<Attr> &attrs, Style *st, const std::vector<CssRule> *css = nullptr, const char *el_name = nullptr,
                        size_t el_name_len = 0) {
     static const char *kProps[] = {"fill", "stroke", "stroke-width", "fill-rule", "fill-opacity", "stroke-opacity", "display", "visibility",
-                                   "stroke-linecap", "stroke-linejoin", "stroke-miterlimit"};
+                                   "stroke-linecap", "stroke-linejoin", "stroke-miterlimit", "stroke-dasharray", "stroke-dashoffset"};
     for (const char *pn : kProps)
         if (const Attr *a = Find(attrs, pn)) ApplyProperty(pn, Trim(a->val, a->val_len), st);
     double opacity_factor = 1.0;  // not inherited: the element's own value multiplies the ancestors'
@@ -1275,6 +1303,13 @@ int ParseRange(Doc *doc, const char *text, const char *end, const Style &initial
                         const double det = std::fabs(st.ctm.a * st.ctm.d - st.ctm.b * st.ctm.c);
                         path.stroke_width = st.ctm.IsIdentity() ? st.stroke_width : static_cast<float>(st.stroke_width * std::sqrt(det));
                         if (flags & PM_SVG_STROKE_STYLES) path.flags |= PM_PATH_STROKE_STYLE(st.cap, st.join, st.miter_half);
+                        if ((flags & PM_SVG_STROKE_DASHES) && !st.dash.empty()) {  // scaled like the width
+                            const double k = st.ctm.IsIdentity() ? 1.0 : std::sqrt(det);
+                            auto scaled = [&](float v) { return st.ctm.IsIdentity() ? v : static_cast<float>(v * k); };
+                            out->dashes.push_back(pm_path_dash{static_cast<uint32_t>(out->paths.size()), static_cast<uint32_t>(out->dash_values.size()),
+                                                               static_cast<uint32_t>(st.dash.size()), scaled(st.dash_offset)});
+                            for (float v : st.dash) out->dash_values.push_back(scaled(v));
+                        }
                     }
                     if (path.flags & (PM_PATH_FILL | PM_PATH_STROKE)) out->paths.push_back(path);
                     else out->els.resize(el0);
@@ -1334,6 +1369,10 @@ pm_svg *pm_svg_parse(const char *text, size_t len, int flags, int *err) {
         *err = PM_ERR_INVALID;
         return nullptr;
     }
+    if ((flags & PM_SVG_STROKE_DASHES) && !(flags & PM_SVG_STROKE_STYLES)) {  // (a dashed stroke is a styled one)
+        *err = PM_ERR_INVALID;
+        return nullptr;
+    }
     pm_svg *s = new (std::nothrow) pm_svg();
     if (!s) {
         *err = PM_ERR_CAPACITY;
@@ -1356,6 +1395,10 @@ size_t pm_svg_n_paths(const pm_svg *s) { return s ? s->paths.size() : 0; }
 size_t pm_svg_n_els(const pm_svg *s) { return s ? s->els.size() : 0; }
 const pm_path *pm_svg_paths(const pm_svg *s) { return s ? s->paths.data() : nullptr; }
 const pm_path_el *pm_svg_els(const pm_svg *s) { return s ? s->els.data() : nullptr; }
+const pm_path_dash *pm_svg_dashes(const pm_svg *s) { return s ? s->dashes.data() : nullptr; }
+size_t pm_svg_n_dashes(const pm_svg *s) { return s ? s->dashes.size() : 0; }
+const float *pm_svg_dash_values(const pm_svg *s) { return s ? s->dash_values.data() : nullptr; }
+size_t pm_svg_n_dash_values(const pm_svg *s) { return s ? s->dash_values.size() : 0; }
 int pm_svg_viewbox(const pm_svg *s, double viewbox[4], double *width, double *height) {
     if (!s) return 0;
     if (viewbox) std::memcpy(viewbox, s->viewbox, sizeof(s->viewbox));

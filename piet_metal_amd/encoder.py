@@ -145,19 +145,45 @@ _PATH_DTYPE = np.dtype(
     [("el_begin", "<u4"), ("el_end", "<u4"), ("flags", "<u4"), ("fill_rgba", "<u4"), ("stroke_rgba", "<u4"), ("stroke_width", "<f4")]
 )
 _EL_DTYPE = np.dtype([("tag", "<u4"), ("pad", "<u4"), ("p", "<f8", (6,))])
-assert _PATH_DTYPE.itemsize == 24 and _EL_DTYPE.itemsize == 56
+_DASH_DTYPE = np.dtype([("path", "<u4"), ("first", "<u4"), ("count", "<u4"), ("offset", "<f4")])
+assert _PATH_DTYPE.itemsize == 24 and _EL_DTYPE.itemsize == 56 and _DASH_DTYPE.itemsize == 16
+
+
+def _dash_arrays(table: dict):
+    """{path: (values, offset)} -> (dashes, dash_values) in the layout of pm_flatten_and_encode_dashed, ascending by path."""
+    dashes = np.zeros(len(table), _DASH_DTYPE)
+    values = []
+    at = 0
+    for k, i in enumerate(sorted(table)):
+        v, off = table[i]
+        dashes[k] = (i, at, len(v), off)
+        values.append(np.asarray(v, np.float32))
+        at += len(v)
+    return dashes, (np.concatenate(values) if values else np.zeros(0, np.float32))
 
 
 class PathSet:
     """Parsed paths: `paths` (structured, 24 B) and `els` (structured, 56 B) arrays
-    in the layout of pm_path / pm_path_el."""
+    in the layout of pm_path / pm_path_el; optionally a dash table (decision D15): `dashes`
+    (structured, 16 B, pm_path_dash, ascending by path) and the f32 `dash_values` they index."""
 
     PATH_DTYPE = _PATH_DTYPE
     EL_DTYPE = _EL_DTYPE
+    DASH_DTYPE = _DASH_DTYPE
 
-    def __init__(self, paths: np.ndarray, els: np.ndarray):
+    def __init__(self, paths: np.ndarray, els: np.ndarray, dashes: np.ndarray | None = None, dash_values: np.ndarray | None = None):
         self.paths = np.ascontiguousarray(paths, dtype=_PATH_DTYPE)
         self.els = np.ascontiguousarray(els, dtype=_EL_DTYPE)
+        self.dashes = np.ascontiguousarray(dashes if dashes is not None else np.zeros(0, _DASH_DTYPE), dtype=_DASH_DTYPE)
+        self.dash_values = np.ascontiguousarray(dash_values if dash_values is not None else np.zeros(0, np.float32), dtype=np.float32)
+
+    def _like(self, paths, els, dashes=None, dash_values=None) -> "PathSet":
+        """A set of these arrays that keeps this one's dash table (unless given) and document attributes."""
+        out = PathSet(paths, els, self.dashes if dashes is None else dashes, self.dash_values if dash_values is None else dash_values)
+        for k in ("viewbox", "size"):
+            if hasattr(self, k):
+                setattr(out, k, getattr(self, k))
+        return out
 
     @classmethod
     def _from_handle(cls, lib, h) -> "PathSet":
@@ -165,11 +191,14 @@ class PathSet:
             npaths, nels = lib.pm_svg_n_paths(h), lib.pm_svg_n_els(h)
             paths = np.frombuffer(C.string_at(lib.pm_svg_paths(h), npaths * 24), dtype=_PATH_DTYPE).copy() if npaths else np.zeros(0, _PATH_DTYPE)
             els = np.frombuffer(C.string_at(lib.pm_svg_els(h), nels * 56), dtype=_EL_DTYPE).copy() if nels else np.zeros(0, _EL_DTYPE)
+            ndash, nval = lib.pm_svg_n_dashes(h), lib.pm_svg_n_dash_values(h)
+            dashes = np.frombuffer(C.string_at(lib.pm_svg_dashes(h), ndash * 16), dtype=_DASH_DTYPE).copy() if ndash else None
+            values = np.frombuffer(C.string_at(lib.pm_svg_dash_values(h), nval * 4), dtype=np.float32).copy() if nval else None
             vb, w, hh = (C.c_double * 4)(), C.c_double(0), C.c_double(0)
             has_vb = lib.pm_svg_viewbox(h, vb, C.byref(w), C.byref(hh))
         finally:
             lib.pm_svg_free(h)
-        ps = cls(paths, els)
+        ps = cls(paths, els, dashes, values)
         ps.viewbox = tuple(vb) if has_vb else None  # the outermost <svg>'s viewBox (user units)
         ps.size = (w.value, hh.value)                # its width / height in px (0: not given)
         return ps
@@ -189,18 +218,20 @@ class PathSet:
 
     @classmethod
     def from_svg(cls, text: bytes | str, reject_arc_paths: bool = False, spec_defaults: bool = False, flat_gradients: bool = False,
-                 stroke_styles: bool = False) -> "PathSet":
+                 stroke_styles: bool = False, stroke_dashes: bool = False) -> "PathSet":
         """Parse an SVG document.  spec_defaults: SVG's initial `fill: black` instead of the
         reference's rule that only a fill property fills (src/lib.rs:299); flat_gradients: a
         url(#gradient) paint becomes the mean colour of the gradient's stops instead of `none`;
         stroke_styles: stroke-linecap / stroke-linejoin / stroke-miterlimit are read and every stroke
-        is drawn as its outline (decision D14) instead of the round poly-line."""
+        is drawn as its outline (decision D14) instead of the round poly-line; stroke_dashes (needs
+        stroke_styles): stroke-dasharray / stroke-dashoffset are read into the dash table (decision D15)."""
         lib = _lib.load()
         data = text.encode() if isinstance(text, str) else bytes(text)
         err = C.c_int(0)
         flags = (_lib.PM_SVG_REJECT_ARC_PATHS if reject_arc_paths else 0) | (_lib.PM_SVG_SPEC_DEFAULTS if spec_defaults else 0)
         flags |= _lib.PM_SVG_FLAT_GRADIENTS if flat_gradients else 0
         flags |= _lib.PM_SVG_STROKE_STYLES if stroke_styles else 0
+        flags |= _lib.PM_SVG_STROKE_DASHES if stroke_dashes else 0
         h = lib.pm_svg_parse(data, len(data), flags, C.byref(err))
         if not h:
             raise _lib.PietMetalError(err.value, "pm_svg_parse")
@@ -233,11 +264,24 @@ class PathSet:
         chosen[slice(None) if select is None else select] = True
         chosen &= (p["flags"] & _lib.PM_PATH_STROKE) != 0
         p["flags"][chosen] = (p["flags"][chosen] & ~np.uint32(_lib.PM_PATH_STROKE_STYLE_MASK)) | np.uint32(style)
-        out = PathSet(p, self.els)
-        for k in ("viewbox", "size"):
-            if hasattr(self, k):
-                setattr(out, k, getattr(self, k))
-        return out
+        return self._like(p, self.els)
+
+    def with_dashes(self, pattern, offset: float = 0.0, select=None) -> "PathSet":
+        """A copy whose stroked, outlined paths (all of them, or those of `select`: indices or a boolean mask) are dashed with
+        `pattern` (1 .. 32 finite lengths >= 0 in user units, alternately dash and gap; an odd count repeats once) starting `offset`
+        into it (decision D15).  Paths without PM_PATH_STROKE | PM_PATH_STROKE_OUTLINE are left alone (with_stroke_style first);
+        a path that had a pattern gets the new one."""
+        pat = np.asarray(pattern, np.float32).reshape(-1)
+        if not (1 <= len(pat) <= 32 and np.all(np.isfinite(pat)) and np.all(pat >= 0) and np.isfinite(np.float32(offset))):
+            raise ValueError("a dash pattern is 1 .. 32 finite values >= 0 and a finite offset")
+        need = np.uint32(_lib.PM_PATH_STROKE | _lib.PM_PATH_STROKE_OUTLINE)
+        chosen = np.zeros(len(self.paths), bool)
+        chosen[slice(None) if select is None else select] = True
+        chosen &= (self.paths["flags"] & need) == need
+        table = {int(d["path"]): (self.dash_values[int(d["first"]) : int(d["first"]) + int(d["count"])], float(d["offset"])) for d in self.dashes}
+        for i in np.flatnonzero(chosen):
+            table[int(i)] = (pat, float(offset))
+        return self._like(self.paths, self.els, *_dash_arrays(table))
 
     def fills_only(self) -> "PathSet":
         p = self.paths.copy()
@@ -247,6 +291,7 @@ class PathSet:
     @staticmethod
     def concat(sets: list["PathSet"]) -> "PathSet":
         paths, els, base = [], [], 0
+        dashes, values, pbase, vbase = [], [], 0, 0
         for s in sets:
             p = s.paths.copy()
             p["el_begin"] += base
@@ -254,7 +299,14 @@ class PathSet:
             base += len(s.els)
             paths.append(p)
             els.append(s.els)
-        return PathSet(np.concatenate(paths), np.concatenate(els))
+            d = s.dashes.copy()
+            d["path"] += pbase
+            d["first"] += vbase
+            pbase += len(s.paths)
+            vbase += len(s.dash_values)
+            dashes.append(d)
+            values.append(s.dash_values)
+        return PathSet(np.concatenate(paths), np.concatenate(els), np.concatenate(dashes), np.concatenate(values))
 
     def transformed(self, affine) -> "PathSet":
         """Apply an affine [a b c d e f] to the element coordinates on the host
@@ -265,4 +317,4 @@ class PathSet:
         x, y = p[:, 0::2].copy(), p[:, 1::2].copy()
         p[:, 0::2] = a * x + c * y + e
         p[:, 1::2] = b * x + d * y + f
-        return PathSet(self.paths, els)
+        return PathSet(self.paths, els, self.dashes, self.dash_values)  # (dash lengths are in user units: width_scale scales them)

@@ -97,9 +97,19 @@ class Renderer:
         self.upload_scene(int(a.size))
 
     def flatten_and_encode(self, paths: PathSet, affine, width_scale: float) -> tuple[int, int]:
-        """On-device flatten + encode; returns (scene_bytes, n_items)."""
+        """On-device flatten + encode; returns (scene_bytes, n_items).  A set with a dash table (PathSet.with_dashes,
+        from_svg(stroke_dashes=True)) goes through pm_flatten_and_encode_dashed."""
         aff = (C.c_double * 6)(*[float(v) for v in affine])
         nbytes, nitems = C.c_size_t(0), C.c_uint32(0)
+        if len(paths.dashes):
+            _lib.check(
+                self._lib.pm_flatten_and_encode_dashed(
+                    self._h, paths.paths.ctypes.data, len(paths.paths), paths.els.ctypes.data, len(paths.els), paths.dashes.ctypes.data,
+                    len(paths.dashes), paths.dash_values.ctypes.data, len(paths.dash_values), aff, float(width_scale), C.byref(nbytes), C.byref(nitems),
+                ),
+                "pm_flatten_and_encode_dashed",
+            )
+            return nbytes.value, nitems.value
         _lib.check(
             self._lib.pm_flatten_and_encode(
                 self._h, paths.paths.ctypes.data, len(paths.paths), paths.els.ctypes.data, len(paths.els), aff,
