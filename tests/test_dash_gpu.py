@@ -4,6 +4,7 @@ paths, which a second renderer makes -- no tolerance, no case left out.  What th
 items is checked against the oracle's renderer and np_hit, which know nothing of dashes.
 
 The `small` tests are also what tests/test_dash_cpu.py runs against the emulated library on a box without a GPU."""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -31,15 +32,15 @@ def plain(pm, ps):
     return pm.PathSet(np_stroke.unstyled(ps.paths), ps.els)
 
 
-def dashed_scene_checks(pm, r, ps, affine, scale, reflatten=False):
+def dashed_scene_checks(pm, r, ps, affine, scale, reflatten=False, r0=None):
     """Flattens (or re-flattens) ps; the scene must be np_dash applied to the poly-line scene of the same paths under the same
-    view.  Returns the scene bytes."""
+    view, which a second renderer makes (r0, or one of its own).  Returns the scene bytes."""
     if reflatten:
         nbytes, n_items = r.reflatten(affine, scale)
     else:
         nbytes, n_items = r.flatten_and_encode(ps, affine, scale)
     got = r.download_scene()
-    with pm.Renderer(0) as r0:
+    with contextlib.nullcontext(r0) if r0 is not None else pm.Renderer(0) as r0:
         nbytes0, n_items0 = r0.flatten_and_encode(plain(pm, ps), affine, scale)
         scene0 = r0.download_scene()
         paths0 = r0.item_paths()
