@@ -219,6 +219,10 @@ const pm_path_dash *pm_svg_dashes(const pm_svg *s);
 size_t pm_svg_n_dashes(const pm_svg *s);
 const float *pm_svg_dash_values(const pm_svg *s);
 size_t pm_svg_n_dash_values(const pm_svg *s);
+/* pm_svg_n_paths entries: for every path the ordinal, among the element children of the outermost <svg>, of the child whose
+ * subtree drew it (for a <use>: the child where the <use> stands, not where its target is defined) -- the document's top-level
+ * groups, as pm_path_groups takes them (decision D16). */
+const uint32_t *pm_svg_path_groups(const pm_svg *s);
 uint32_t pm_parse_color(const char *s); /* parse_color src/lib.rs:375-385 */
 
 /* ==== 3. renderer (replaces PietRenderer, TestApp/PietRenderer.{h,m}) ========= */
@@ -267,6 +271,26 @@ int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths,
  * re-encodes on the CPU when the view changes (PietRenderer.m:90-101, :145); here a view change
  * is four small kernels plus the scene index. */
 int pm_reflatten(pm_ctx *c, const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
+/* Animating objects, not only the camera (decision D16): pm_reflatten with one transform PER GROUP of paths.
+ * pm_path_groups assigns every resident path a group index; pm_reflatten_groups flattens path p under
+ * xforms[group_of_path[p]]: its affine (kurbo order, binary64) and its width_scale (f32, NOT derived from the matrix on the
+ * device: the caller's, as with pm_reflatten).  The scene is, byte for byte, what D1-D15 define when every path takes its own
+ * group's two values wherever they appear (subdivision counts, points, widths, the thin-line rule, boxes, outlines, dashes);
+ * item order, *n_items, pm_item_paths and the layout do not depend on the table.  A table whose entries are all equal gives
+ * pm_reflatten's bytes. */
+typedef struct {
+    double m[6];
+    float width_scale;
+    uint32_t reserved; /* 0 */
+} pm_group_xform;      /* 56 bytes */
+/* group_of_path[n_paths]; n_paths must equal the resident path count (pm_flatten_and_encode[_dashed]).  The map stays resident
+ * with the paths: a later pm_flatten_and_encode* forgets it, pm_reflatten ignores and keeps it.  PM_ERR_INVALID: no resident
+ * paths, a NULL pointer, another n_paths. */
+int pm_path_groups(pm_ctx *c, const uint32_t *group_of_path, size_t n_paths);
+/* Same outputs, same PM_ERR_CAPACITY contract and the same grow-and-retry as pm_reflatten; the table is copied before the call
+ * returns.  PM_ERR_INVALID: no resident paths or no resident map, a NULL pointer, n_groups == 0 or not above the largest index
+ * of the map (a longer table is fine), a non-zero `reserved`. */
+int pm_reflatten_groups(pm_ctx *c, const pm_group_xform *xforms, size_t n_groups, size_t *scene_bytes, uint32_t *n_items);
 /* pm_flatten_and_encode with a dash table (decision D15): the styled stroke of every path named in `dashes` is cut into dashes
  * on the device.  A dashed stroke stays ONE compound Fill item per sub-path in the poly-line's slot -- *n_items and pm_item_paths
  * do not change -- whose entries are the D14 outlines of its dashes.  `dashes` is strictly ascending by path; PM_ERR_INVALID: an

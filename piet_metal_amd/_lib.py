@@ -85,7 +85,11 @@ class Cmd(C.Structure):
     _fields_ = [("tag", C.c_uint32), ("body", C.c_uint32 * 5)]
 
 
-assert C.sizeof(PathEl) == 56 and C.sizeof(Path) == 24 and C.sizeof(Cmd) == 24
+class GroupXform(C.Structure):  # pm_group_xform (decision D16): one group's affine (kurbo order) and width_scale
+    _fields_ = [("m", C.c_double * 6), ("width_scale", C.c_float), ("reserved", C.c_uint32)]
+
+
+assert C.sizeof(PathEl) == 56 and C.sizeof(Path) == 24 and C.sizeof(Cmd) == 24 and C.sizeof(GroupXform) == 56
 
 # name -> (restype, argtypes); every symbol include/piet_metal_amd.h declares
 SIGNATURES = {
@@ -121,6 +125,7 @@ SIGNATURES = {
     "pm_svg_n_dashes": (C.c_size_t, [C.c_void_p]),
     "pm_svg_dash_values": (C.c_void_p, [C.c_void_p]),
     "pm_svg_n_dash_values": (C.c_size_t, [C.c_void_p]),
+    "pm_svg_path_groups": (C.c_void_p, [C.c_void_p]),
     "pm_parse_color": (C.c_uint32, [C.c_char_p]),
     "pm_create": (C.c_void_p, [C.c_int, C.POINTER(C.c_int)]),
     "pm_destroy": (None, [C.c_void_p]),
@@ -135,6 +140,8 @@ SIGNATURES = {
     "pm_flatten_and_encode_dashed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
                                                C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "pm_reflatten": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "pm_path_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "pm_reflatten_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "pm_download_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pm_render": (C.c_int, [C.c_void_p]),
     "pm_render_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -4,6 +4,7 @@
     python -m piet_metal_amd.cli drawing.svg out.png --scale 4 --width 1024 --height 1024
 
     python -m piet_metal_amd.cli tiger spin.png --frames 60 --spin 360     (spin-000.png ... spin-059.png)
+    python -m piet_metal_amd.cli drawing.svg apart.png --frames 30 --explode 1.5    (the top-level groups move apart)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -12,7 +13,8 @@ bench.py and read back once.  Files are read with the SVG front-end's full docum
 transforms, style, opacity, fill-rule, basic shapes; SVG's initial `fill: black`); `tiger` is the
 embedded asset read as make_tiger reads it (src/lib.rs:286-328).  --frames renders an animation the
 way the reference's view does on every change (PietRenderer.m:90-101, :145): the scene is encoded
-again for each frame -- here by re-flattening the resident paths on the device (pm_reflatten).
+again for each frame -- here by re-flattening the resident paths on the device (pm_reflatten; with
+--explode pm_reflatten_groups, one affine per top-level group of the document).
 """
 from __future__ import annotations
 
@@ -77,6 +79,7 @@ def main(argv=None) -> int:
     ap.add_argument("--stroke-dashes", action="store_true", help="files: also read stroke-dasharray / stroke-dashoffset and cut the outlined strokes into dashes (implies --stroke-styles)")
     ap.add_argument("--frames", type=int, default=1, help="render an animation of this many frames (output NAME-###.png)")
     ap.add_argument("--spin", type=float, default=360.0, help="--frames: total rotation about the viewport centre, degrees")
+    ap.add_argument("--explode", type=float, default=None, metavar="F", help="--frames N (>= 2): instead of spinning, frame k moves every top-level group of the document (element child of the outermost <svg>) by F * k / (N - 1) * (its centre - the document's centre); the groups are re-flattened on the device, each under its own affine")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
     args = ap.parse_args(argv)
     try:
@@ -85,15 +88,18 @@ def main(argv=None) -> int:
             raise ValueError
     except ValueError:
         ap.error("--pick takes X,Y")
+    if args.explode is not None and args.frames < 2:
+        ap.error("--explode needs --frames N with N >= 2")
 
     from . import PathSet, Renderer
 
     if args.input == "tiger":
-        paths = PathSet.tiger(args.reject_arc_paths)
+        paths = PathSet.tiger(args.reject_arc_paths, groups=args.explode is not None)
     else:
         with open(args.input, "rb") as f:
             paths = PathSet.from_svg(f.read(), args.reject_arc_paths, spec_defaults=not args.reference_fill_rule, flat_gradients=not args.no_flat_gradients,
-                                     stroke_styles=args.stroke_styles or args.stroke_dashes, stroke_dashes=args.stroke_dashes)
+                                     stroke_styles=args.stroke_styles or args.stroke_dashes, stroke_dashes=args.stroke_dashes,
+                                     groups=args.explode is not None)
     scale = args.scale if args.scale is not None else args.height / 200.0
     off = args.offset if args.offset is not None else ((args.width - args.height) / 2.0 if args.scale is None else 0.0, 0.0)
     base = (scale, 0.0, 0.0, scale, float(off[0]), float(off[1]))
@@ -120,16 +126,55 @@ def main(argv=None) -> int:
         stem = args.output[:-4] if args.output.lower().endswith(".png") else args.output
         cx, cy = args.width / 2.0, args.height / 2.0
         t_gpu = 0.0
+        away = group_offsets(paths) if args.explode is not None else None
         for k in range(args.frames):
             aff = spin_affine(base, math.radians(args.spin * k / args.frames), cx, cy)
             t0 = time.perf_counter()
-            nbytes, nitems = r.reflatten(aff, scale)  # the per-frame re-encode, on the device
+            if away is not None:  # every top-level group under its own affine: base after a translation in user units
+                affs = explode_affines(base, away * (args.explode * k / (args.frames - 1)))
+                nbytes, nitems = r.reflatten_groups(affs, np.full(len(affs), scale, np.float32))
+            else:
+                nbytes, nitems = r.reflatten(aff, scale)  # the per-frame re-encode, on the device
             r.render()
             r.sync()
             t_gpu += time.perf_counter() - t0
             write_png(f"{stem}-{k:03d}.png", r.read_pixels())
         print(f"{stem}-###.png: {args.frames} frames {args.width}x{args.height}, re-encode + render {t_gpu / args.frames * 1e3:.2f} ms per frame", file=sys.stderr)
     return 0
+
+
+def group_offsets(paths) -> np.ndarray:
+    """(G, 2): for every group of paths.groups the centre of the box of its elements' coordinates (control points included)
+    minus the centre of the box of all of them, in user units; a group without coordinates stays where it is."""
+    els, tags = paths.els, paths.els["tag"]
+    used = np.zeros((len(els), 6), bool)  # which of p[0..6) an element's tag gives a meaning to
+    for tag, n in ((0, 2), (1, 2), (2, 4), (3, 6)):  # MoveTo, LineTo, QuadTo, CurveTo
+        used[tags == tag, :n] = True
+    group_of_el = np.repeat(paths.groups, paths.paths["el_end"] - paths.paths["el_begin"])
+
+    def centre(mask):
+        m = used & mask[:, None]
+        if not m.any():
+            return None
+        x, y = els["p"][:, 0::2][m[:, 0::2]], els["p"][:, 1::2][m[:, 1::2]]
+        return np.array([(x.min() + x.max()) / 2.0, (y.min() + y.max()) / 2.0])
+
+    doc = centre(np.ones(len(els), bool))
+    out = np.zeros((paths.n_groups(), 2))
+    for g in range(len(out)):
+        c = centre(group_of_el == g)
+        if c is not None:
+            out[g] = c - doc
+    return out
+
+
+def explode_affines(base, shifts) -> np.ndarray:
+    """(G, 6): `base` after a translation by shifts[g] (user units), per group."""
+    a, b, c, d, e, f = base
+    out = np.tile(np.array(base, np.float64), (len(shifts), 1))
+    out[:, 4] = e + a * shifts[:, 0] + c * shifts[:, 1]
+    out[:, 5] = f + b * shifts[:, 0] + d * shifts[:, 1]
+    return out
 
 
 def spin_affine(base, theta: float, cx: float, cy: float):

@@ -2018,7 +2018,7 @@ int pm_upload_scene(pm_ctx *c, size_t bytes) {
 
 namespace {
 int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els, const pm::DashTable *dash,
-                     const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
+                     const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items, bool grouped = false);
 }
 
 int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
@@ -2046,7 +2046,7 @@ int pm_flatten_and_encode_dashed(pm_ctx *c, const pm_path *paths, size_t n_paths
 
 namespace {
 int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els, const pm::DashTable *dash,
-                     const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items) {
+                     const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items, bool grouped) {
     PM_TRY(hipSetDevice(c->device));
     size_t bytes = 0;
     uint32_t items = 0;
@@ -2068,7 +2068,7 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
     int r = grow_alt(c->dev_scene_cap);
     if (r == PM_OK)
         r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, dash, affine, width_scale, c->d_scene_alt,
-                                      c->dev_scene_alt_cap, &bytes, &items, &he);
+                                      c->dev_scene_alt_cap, &bytes, &items, &he, grouped);
     // (a dash table: the dashes of a scene whose poly-lines did not fit are counted by the call after the one that made room for them)
     for (int attempt = 0; attempt < (c->flatten_cache.n_dashes ? 2 : 1) && r == PM_ERR_CAPACITY && bytes > c->dev_scene_alt_cap; ++attempt) {
         // grow it (the kernels write it; nothing is staged on the host) and retry once.  `bytes` is the exact need (the point count
@@ -2076,7 +2076,7 @@ int FlattenAndEncode(pm_ctx *c, bool resident, const pm_path *paths, size_t n_pa
         r = grow_alt(std::max<size_t>(bytes, std::min<size_t>(bytes + (bytes >> 3), 0xffffffffull)));
         if (r == PM_OK)
             r = pm::FlattenEncodeOnDevice(c->stream, &c->flatten_cache, resident, paths, n_paths, els, n_els, dash, affine, width_scale, c->d_scene_alt,
-                                          c->dev_scene_alt_cap, &bytes, &items, &he);
+                                          c->dev_scene_alt_cap, &bytes, &items, &he, grouped);
     }
     const float flatten_ms = timer.ms();
     {
@@ -2112,6 +2112,59 @@ int pm_reflatten(pm_ctx *c, const double affine[6], float width_scale, size_t *s
     }
     c->replan_wide = true;  // (a view change: the next plan is made to last, EnsureArena)
     return FlattenAndEncode(c, true, nullptr, 0, nullptr, 0, nullptr, affine, width_scale, scene_bytes, n_items);
+}
+
+int pm_path_groups(pm_ctx *c, const uint32_t *group_of_path, size_t n_paths) {
+    if (!c || !group_of_path) {
+        SetError("pm_path_groups: NULL argument");
+        return PM_ERR_INVALID;
+    }
+    if (!c->flatten_cache.resident) {
+        SetError("pm_path_groups: no paths resident (pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    if (n_paths != c->flatten_cache.n_paths) {
+        SetError("pm_path_groups: n_paths is " + std::to_string(n_paths) + ", " + std::to_string(c->flatten_cache.n_paths) + " paths are resident");
+        return PM_ERR_INVALID;
+    }
+    PM_TRY(hipSetDevice(c->device));
+    hipError_t he = hipSuccess;
+    const int r = pm::FlattenSetPathGroups(c->stream, &c->flatten_cache, group_of_path, n_paths, &he);
+    if (r == PM_ERR_HIP) return HipFail(he, "pm_path_groups");
+    return r;
+}
+
+int pm_reflatten_groups(pm_ctx *c, const pm_group_xform *xforms, size_t n_groups, size_t *scene_bytes, uint32_t *n_items) {
+    if (!c || !xforms) {
+        SetError("pm_reflatten_groups: NULL argument");
+        return PM_ERR_INVALID;
+    }
+    if (!c->flatten_cache.resident) {
+        SetError("pm_reflatten_groups: no paths resident (pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    if (!c->flatten_cache.has_groups) {
+        SetError("pm_reflatten_groups: no group map resident (pm_path_groups after pm_flatten_and_encode)");
+        return PM_ERR_INVALID;
+    }
+    if (n_groups == 0 || n_groups <= c->flatten_cache.max_group) {
+        SetError("pm_reflatten_groups: " + std::to_string(n_groups) + " transforms for a group map that reaches index " +
+                 std::to_string(c->flatten_cache.max_group));
+        return PM_ERR_INVALID;
+    }
+    for (size_t g = 0; g < n_groups; ++g) {
+        if (xforms[g].reserved != 0) {
+            SetError("pm_reflatten_groups: reserved must be 0 (transform " + std::to_string(g) + ")");
+            return PM_ERR_INVALID;
+        }
+    }
+    PM_TRY(hipSetDevice(c->device));
+    hipError_t he = hipSuccess;
+    // (the one copy of the table, in front of the kernels; a grow-and-retry finds it where it is)
+    if (pm::FlattenStageGroupTable(c->stream, &c->flatten_cache, xforms, n_groups, &he) != PM_OK) return HipFail(he, "pm_reflatten_groups");
+    c->replan_wide = true;  // (as pm_reflatten: the next plan is made to last, EnsureArena)
+    const double unused[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0};
+    return FlattenAndEncode(c, true, nullptr, 0, nullptr, 0, nullptr, unused, 1.0f, scene_bytes, n_items, true);
 }
 
 int pm_download_scene(pm_ctx *c, uint8_t *dst, size_t cap, size_t *bytes) {

@@ -192,17 +192,19 @@ __device__ __forceinline__ DashPlan PlanOf(const DashPattern &pat, unsigned long
 __device__ __forceinline__ pm_path_dash DashOf(const pm_path_dash *dashes, uint32_t ix) { return dashes[ix]; }
 
 // A wave per dashed sub-path: out_cnt[s] = the entries of its item, added to *out_total (before KOutlineScan).
-__global__ __launch_bounds__(256) void KDashCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
-                                                  const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
-                                                  const uint32_t *sub_first_el, const uint32_t *totals, const unsigned long long *n_pts64,
-                                                  const uint32_t *path_dash, const pm_path_dash *dashes, const float *dash_values, const uint8_t *scene,
-                                                  uint32_t scene_cap, uint32_t *out_cnt, unsigned long long *out_total) {
-    __shared__ unsigned long long s_pf[kDashWaves][66];
+template <bool kGrouped>
+__device__ __forceinline__ void DashCountBody(unsigned long long (*s_pf)[66], const pm_path *paths, uint32_t n_paths, const pm_path_el *els,
+                                              float width_scale_u, const GroupTable &gt, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                                              const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                                              const uint32_t *totals, const unsigned long long *n_pts64, const uint32_t *path_dash,
+                                              const pm_path_dash *dashes, const float *dash_values, const uint8_t *scene, uint32_t scene_cap,
+                                              uint32_t *out_cnt, unsigned long long *out_total) {
     const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u, wave = (threadIdx.x >> 6) & (kDashWaves - 1u);
     if (s >= totals[2]) return;  // (whole waves)
-    const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals[0], s);
+    const OutlineJob job = MakeOutlineJob<kGrouped>(paths, n_paths, els, width_scale_u, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals[0], s);
     if (!job.styled || !IsDashed(path_dash, job.path)) return;  // (uniform)
+    const float width_scale = WidthScaleOf<kGrouped>(width_scale_u, gt, job.path);
     const DashPattern pat = LoadPattern(s_pf[wave], DashOf(dashes, path_dash[job.path]), dash_values, width_scale, lane);
     const OutlineLayout lay = LayoutOf(job);
     unsigned long long total = lay.total;
@@ -233,6 +235,27 @@ __global__ __launch_bounds__(256) void KDashCount(const pm_path *paths, uint32_t
         out_cnt[s] = static_cast<uint32_t>(total);
         if (total) atomicAdd(out_total, total);
     }
+}
+
+__global__ __launch_bounds__(256) void KDashCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
+                                                  const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
+                                                  const uint32_t *sub_first_el, const uint32_t *totals, const unsigned long long *n_pts64,
+                                                  const uint32_t *path_dash, const pm_path_dash *dashes, const float *dash_values, const uint8_t *scene,
+                                                  uint32_t scene_cap, uint32_t *out_cnt, unsigned long long *out_total) {
+    __shared__ unsigned long long s_pf[kDashWaves][66];
+    DashCountBody<false>(s_pf, paths, n_paths, els, width_scale, GroupTable{nullptr, nullptr}, el_ptoff, el_mvoff, path_item_base, path_pt_base,
+                         sub_first_el, totals, n_pts64, path_dash, dashes, dash_values, scene, scene_cap, out_cnt, out_total);
+}
+
+__global__ __launch_bounds__(256) void KDashCountGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, GroupTable gt,
+                                                         const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+                                                         const uint32_t *path_pt_base, const uint32_t *sub_first_el, const uint32_t *totals,
+                                                         const unsigned long long *n_pts64, const uint32_t *path_dash, const pm_path_dash *dashes,
+                                                         const float *dash_values, const uint8_t *scene, uint32_t scene_cap, uint32_t *out_cnt,
+                                                         unsigned long long *out_total) {
+    __shared__ unsigned long long s_pf[kDashWaves][66];
+    DashCountBody<true>(s_pf, paths, n_paths, els, 0.0f, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals, n_pts64,
+                        path_dash, dashes, dash_values, scene, scene_cap, out_cnt, out_total);
 }
 
 // What a lane knows of its segment k during one step of KDash (LDS, a record per lane).
@@ -383,19 +406,21 @@ __device__ __forceinline__ uint32_t FirstAbove(const DashSeg *seg, bool ends, ui
 // scan of the segments' piece counts hands the lanes (dash start -> cap + first quad), (inside vertex -> join + following quad),
 // (dash end -> cap), so that one long segment with a thousand dashes occupies 64 lanes, not one.  A dash that is still open at
 // the end of a step is looked ahead for once (LocateCut) and carried: its outline's layout needs its vertex count.
-__global__ __launch_bounds__(256) void KDash(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
-                                             const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
-                                             const uint32_t *sub_first_el, const uint32_t *totals, const unsigned long long *n_pts64,
-                                             const uint32_t *out_cnt, const uint32_t *out_off, const unsigned long long *out_total, const uint32_t *path_dash,
-                                             const pm_path_dash *dashes, const float *dash_values, uint8_t *scene, uint32_t scene_cap) {
-    __shared__ unsigned long long s_pf[kDashWaves][66];
-    __shared__ DashSeg s_seg[kDashWaves][64];
+template <bool kGrouped>
+__device__ __forceinline__ void DashBody(unsigned long long (*s_pf)[66], DashSeg (*s_seg)[64], const pm_path *paths, uint32_t n_paths,
+                                         const pm_path_el *els, float width_scale_u, const GroupTable &gt, const uint32_t *el_ptoff,
+                                         const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
+                                         const uint32_t *sub_first_el, const uint32_t *totals, const unsigned long long *n_pts64,
+                                         const uint32_t *out_cnt, const uint32_t *out_off, const unsigned long long *out_total,
+                                         const uint32_t *path_dash, const pm_path_dash *dashes, const float *dash_values, uint8_t *scene,
+                                         uint32_t scene_cap) {
     const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u, wave = (threadIdx.x >> 6) & (kDashWaves - 1u);
     const uint32_t n_items = totals[0], n_subs = totals[2];
     if (s >= n_subs || Overfull(n_items, *n_pts64, scene_cap)) return;  // (whole waves)
-    const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
+    const OutlineJob job = MakeOutlineJob<kGrouped>(paths, n_paths, els, width_scale_u, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
     if (!job.styled || !IsDashed(path_dash, job.path)) return;  // (uniform)
+    const float width_scale = WidthScaleOf<kGrouped>(width_scale_u, gt, job.path);
     const DashPattern pat = LoadPattern(s_pf[wave], DashOf(dashes, path_dash[job.path]), dash_values, width_scale, lane);
     const OutlineLayout lay = LayoutOf(job);
     const size_t outlines_start = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize) + 8 * static_cast<size_t>(out_total[1]);
@@ -549,4 +574,27 @@ __global__ __launch_bounds__(256) void KDash(const pm_path *paths, uint32_t n_pa
         cur = nxt;
     }
     WriteOutlineItem(scene, scene_cap, n_items, job, sink, out_cnt[s], lane);
+}
+
+__global__ __launch_bounds__(256) void KDash(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
+                                             const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
+                                             const uint32_t *sub_first_el, const uint32_t *totals, const unsigned long long *n_pts64,
+                                             const uint32_t *out_cnt, const uint32_t *out_off, const unsigned long long *out_total, const uint32_t *path_dash,
+                                             const pm_path_dash *dashes, const float *dash_values, uint8_t *scene, uint32_t scene_cap) {
+    __shared__ unsigned long long s_pf[kDashWaves][66];
+    __shared__ DashSeg s_seg[kDashWaves][64];
+    DashBody<false>(s_pf, s_seg, paths, n_paths, els, width_scale, GroupTable{nullptr, nullptr}, el_ptoff, el_mvoff, path_item_base, path_pt_base,
+                    sub_first_el, totals, n_pts64, out_cnt, out_off, out_total, path_dash, dashes, dash_values, scene, scene_cap);
+}
+
+__global__ __launch_bounds__(256) void KDashGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, GroupTable gt,
+                                                    const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+                                                    const uint32_t *path_pt_base, const uint32_t *sub_first_el, const uint32_t *totals,
+                                                    const unsigned long long *n_pts64, const uint32_t *out_cnt, const uint32_t *out_off,
+                                                    const unsigned long long *out_total, const uint32_t *path_dash, const pm_path_dash *dashes,
+                                                    const float *dash_values, uint8_t *scene, uint32_t scene_cap) {
+    __shared__ unsigned long long s_pf[kDashWaves][66];
+    __shared__ DashSeg s_seg[kDashWaves][64];
+    DashBody<true>(s_pf, s_seg, paths, n_paths, els, 0.0f, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals, n_pts64,
+                   out_cnt, out_off, out_total, path_dash, dashes, dash_values, scene, scene_cap);
 }

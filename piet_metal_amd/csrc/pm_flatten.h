@@ -33,6 +33,13 @@ struct FlattenCache {
     uint32_t *d_dash = nullptr;
     size_t cap_dash = 0, n_dashes = 0;
     std::vector<uint32_t> h_dash;  // (the staging copy the upload reads)
+    // the group map of the resident paths and the transform table of the last grouped re-flatten (decision D16): a word per path,
+    // n_groups records; h_xforms is the pinned staging copy the table's one upload reads.  All three grow only.
+    uint32_t *d_groups = nullptr;
+    pm_group_xform *d_xforms = nullptr, *h_xforms = nullptr;
+    size_t cap_groups = 0, cap_xforms = 0;
+    bool has_groups = false;   // a map is resident (pm_path_groups since the last upload of paths)
+    uint32_t max_group = 0;    // ... and its largest index
     void Free();
     hipError_t Reserve(size_t n_paths, size_t n_els);  // room for this many paths / elements (pm_create)
 };
@@ -49,9 +56,17 @@ struct DashTable {
 // dash: nullptr or the paths' dash table (ignored with use_resident: the resident one is used again).
 // use_resident: ignore h_paths / h_els and flatten the paths resident in `cache` again.
 // On PM_ERR_CAPACITY *scene_bytes holds the size that would have been needed.
+// grouped (needs use_resident and a resident group map): affine / width_scale are ignored, path p takes those of
+// cache->d_xforms[cache->d_groups[p]] (decision D16; FlattenStageGroupTable put the table there).
 int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resident, const pm_path *h_paths, size_t n_paths, const pm_path_el *h_els,
                           size_t n_els, const DashTable *dash, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
-                          size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error);
+                          size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error, bool grouped = false);
+
+// The group map of the resident paths (n_paths == cache->n_paths, checked by the caller): uploaded, its maximum kept.  Synchronises.
+int FlattenSetPathGroups(hipStream_t stream, FlattenCache *cache, const uint32_t *group_of_path, size_t n_paths, hipError_t *hip_error);
+// The transform table of a grouped re-flatten: through the pinned staging copy (grown only when n_groups grows), one asynchronous
+// copy on `stream` in front of the kernels.
+int FlattenStageGroupTable(hipStream_t stream, FlattenCache *cache, const pm_group_xform *xforms, size_t n_groups, hipError_t *hip_error);
 
 // First item of every resident path in the scene the kernels last wrote (h_base: cache->n_paths entries; path p's items are
 // [h_base[p], h_base[p + 1]), the last path's end at the scene's item count).  Synchronises `stream`.

@@ -49,6 +49,34 @@ __device__ __forceinline__ void Xform(const Affine &a, double x, double y, doubl
     *oy = a.m[1] * x + a.m[3] * y + a.m[5];
 }
 
+// Decision D16: a grouped re-flatten gives path p the affine and width_scale of xforms[group_of_path[p]].  Every kernel that takes
+// the affine or width_scale has two forms, chosen at compile time: the uniform one (pm_flatten_and_encode, pm_reflatten) keeps its
+// by-value kernel argument and never looks at a table; the grouped one (K...Grouped, pm_reflatten_groups) makes one table read per
+// thread where the uniform one reads its argument.  Consecutive elements share a path: a wave's reads hit one or two cache lines.
+struct GroupTable {
+    const uint32_t *group_of_path;  // [n_paths], every index below the table's length (host check, pm_path_groups)
+    const pm_group_xform *xforms;
+};
+
+template <bool kGrouped>
+__device__ __forceinline__ Affine AffineOf(const Affine &aff, const GroupTable &gt, uint32_t p) {
+    if constexpr (kGrouped) {
+        const pm_group_xform *x = gt.xforms + gt.group_of_path[p];
+        Affine a;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) a.m[k] = x->m[k];
+        return a;
+    } else {
+        return aff;
+    }
+}
+
+template <bool kGrouped>
+__device__ __forceinline__ float WidthScaleOf(float width_scale, const GroupTable &gt, uint32_t p) {
+    if constexpr (kGrouped) return gt.xforms[gt.group_of_path[p]].width_scale;
+    else return width_scale;
+}
+
 // End point of the nearest earlier Move/Line/Curve element of the same path
 // (flatten.rs keeps last_pt only across those; QuadTo / ClosePath fall to `_ => ()`).
 __device__ bool LastPoint(const pm_path_el *els, uint32_t el_begin, uint32_t i, const Affine &a, double *lx, double *ly) {
@@ -112,8 +140,9 @@ __device__ __forceinline__ bool Overfull(uint32_t n_items, unsigned long long n_
     return sizeof(SimpleGroup) + static_cast<unsigned long long>(n_items) * (sizeof(ShortBbox) + kItemSize) + 8ull * n_pts64 > scene_cap;
 }
 
-__global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
-                       uint32_t *el_npts, uint32_t *el_move, uint32_t *err, unsigned long long *n_pts64) {
+template <bool kGrouped>
+__device__ __forceinline__ void CountBody(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, const Affine &aff_u,
+                                          const GroupTable &gt, uint32_t *el_npts, uint32_t *el_move, uint32_t *err, unsigned long long *n_pts64) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long q = 0;
     if (i < n_els) {
@@ -142,6 +171,7 @@ __global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el 
                 } else if (tag == PM_EL_LINE) {
                     n = 1;
                 } else {
+                    const Affine aff = AffineOf<kGrouped>(aff_u, gt, p);
                     LastPoint(els, paths[p].el_begin, i, aff, &lx, &ly);
                     double p1x, p1y, p2x, p2y, p3x, p3y;
                     Xform(aff, els[i].p[0], els[i].p[1], &p1x, &p1y);
@@ -165,6 +195,16 @@ __global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el 
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d, 64);
     if ((threadIdx.x & 63u) == 0 && q != 0) atomicAdd(n_pts64, q);
+}
+
+__global__ void KCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
+                       uint32_t *el_npts, uint32_t *el_move, uint32_t *err, unsigned long long *n_pts64) {
+    CountBody<false>(paths, n_paths, els, n_els, aff, GroupTable{nullptr, nullptr}, el_npts, el_move, err, n_pts64);
+}
+
+__global__ void KCountGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, GroupTable gt,
+                              uint32_t *el_npts, uint32_t *el_move, uint32_t *err, unsigned long long *n_pts64) {
+    CountBody<true>(paths, n_paths, els, n_els, Affine{}, gt, el_npts, el_move, err, n_pts64);
 }
 
 // One workgroup.  Exclusive scans with totals at index n.
@@ -369,10 +409,11 @@ __global__ __launch_bounds__(kScanThreads) void KScanApply(uint32_t n_els, uint3
 
 // (n_items and the other totals are read from device memory: the host does not wait for KScan before
 //  it launches the kernels that depend on them)
-__global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
-                        const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
-                        const uint32_t *path_pt_base, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
-                        uint32_t scene_cap, double *el_bbox, uint32_t *sub_first_el) {
+template <bool kGrouped>
+__device__ __forceinline__ void PointsBody(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, const Affine &aff_u,
+                                           const GroupTable &gt, const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                                           const uint32_t *path_pt_base, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
+                                           uint32_t scene_cap, double *el_bbox, uint32_t *sub_first_el) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_els) return;
     const uint32_t n_items = totals[0];
@@ -399,6 +440,7 @@ __global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el
     const size_t base = points_start + 8 * static_cast<size_t>(path_pt_base[p]);
     const size_t dst0 = base + 8 * (static_cast<size_t>(local) + (compound ? sub : 0u));
     const size_t dst1 = base + 8 * (static_cast<size_t>(path_pts) + (compound ? n_sub_path : 0u) + local);  // stroke copy when a fill copy exists
+    const Affine aff = AffineOf<kGrouped>(aff_u, gt, p);
     double bx0, by0, bx1, by1;
     auto emit = [&](uint32_t k, double x, double y) {
         if (k == 0) {
@@ -439,6 +481,22 @@ __global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el
     el_bbox[4 * static_cast<size_t>(i) + 3] = by1;
 }
 
+__global__ void KPoints(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, Affine aff,
+                        const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                        const uint32_t *path_pt_base, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
+                        uint32_t scene_cap, double *el_bbox, uint32_t *sub_first_el) {
+    PointsBody<false>(paths, n_paths, els, n_els, aff, GroupTable{nullptr, nullptr}, el_npts, el_ptoff, el_mvoff, path_pt_base, totals, n_pts64, scene,
+                      scene_cap, el_bbox, sub_first_el);
+}
+
+__global__ void KPointsGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, uint32_t n_els, GroupTable gt,
+                               const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                               const uint32_t *path_pt_base, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
+                               uint32_t scene_cap, double *el_bbox, uint32_t *sub_first_el) {
+    PointsBody<true>(paths, n_paths, els, n_els, Affine{}, gt, el_npts, el_ptoff, el_mvoff, path_pt_base, totals, n_pts64, scene, scene_cap, el_bbox,
+                     sub_first_el);
+}
+
 // The thin-line rule of encode_path_stroke, src/lib.rs:353-362: a stroke narrower than kThinLine is drawn that wide and fainter.
 __device__ __forceinline__ void ThinLine(float *width, uint32_t *rgba) {
     if (*width < kThinLine) {
@@ -465,10 +523,12 @@ __device__ __forceinline__ void WaveBox(double &x0, double &y0, double &x1, doub
 // One WAVE per sub-path: the lanes stride over its elements and the element boxes are united with
 // shuffles (a thread per sub-path walked a 2 488-point outline alone: 57 us of a 0.15 ms re-encode).
 // fmin / fmax are exact and associative: the union is the one Rect::union_pt builds point by point.
-__global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale,
-                       const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
-                       const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
-                       const double *el_bbox, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene, uint32_t scene_cap) {
+template <bool kGrouped>
+__device__ __forceinline__ void ItemsBody(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale_u, const GroupTable &gt,
+                                          const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                                          const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                                          const double *el_bbox, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene,
+                                          uint32_t scene_cap) {
     const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;  // sub-path of this wave
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_items = totals[0], n_subs = totals[2];
@@ -556,6 +616,7 @@ __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el 
     }
     if (has_stroke && lane == 0) {
         // encode_path_stroke + Encoder::polyline, src/lib.rs:353-367, :209-222
+        const float width_scale = WidthScaleOf<kGrouped>(width_scale_u, gt, p);
         float width = path.stroke_width * width_scale;  // src/lib.rs:320
         uint32_t rgba = path.stroke_rgba;
         ThinLine(&width, &rgba);
@@ -572,6 +633,22 @@ __global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el 
             it[5] = it[6] = it[7] = 0;
         }
     }
+}
+
+__global__ void KItems(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale,
+                       const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                       const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                       const double *el_bbox, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene, uint32_t scene_cap) {
+    ItemsBody<false>(paths, n_paths, els, width_scale, GroupTable{nullptr, nullptr}, el_npts, el_ptoff, el_mvoff, path_item_base, path_pt_base,
+                     sub_first_el, el_bbox, totals, n_pts64, scene, scene_cap);
+}
+
+__global__ void KItemsGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, GroupTable gt,
+                              const uint32_t *el_npts, const uint32_t *el_ptoff, const uint32_t *el_mvoff,
+                              const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                              const double *el_bbox, const uint32_t *totals, const unsigned long long *n_pts64, uint8_t *scene, uint32_t scene_cap) {
+    ItemsBody<true>(paths, n_paths, els, 0.0f, gt, el_npts, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, el_bbox, totals, n_pts64,
+                    scene, scene_cap);
 }
 
 #include "pm_stroke_outline.h"
@@ -601,6 +678,9 @@ void FlattenCache::Free() {
     if (d_u32) (void)hipFree(d_u32);
     if (d_bbox) (void)hipFree(d_bbox);
     if (d_dash) (void)hipFree(d_dash);
+    if (d_groups) (void)hipFree(d_groups);
+    if (d_xforms) (void)hipFree(d_xforms);
+    if (h_xforms) (void)hipHostFree(h_xforms);
     if (h_meta) (void)hipHostFree(h_meta);
     *this = FlattenCache();
 }
@@ -643,10 +723,11 @@ hipError_t FlattenCache::Reserve(size_t n_paths, size_t n_els) {
 
 int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resident, const pm_path *h_paths, size_t n_paths, const pm_path_el *h_els,
                           size_t n_els, const DashTable *dash, const double affine[6], float width_scale, uint8_t *d_scene, size_t scene_cap,
-                          size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error) {
+                          size_t *scene_bytes, uint32_t *n_items_out, hipError_t *hip_error, bool grouped) {
     hipError_t hip_err = hipSuccess;
     int status = PM_OK;
     scene_cap = std::min(scene_cap, SceneCapLimit());
+    if (grouped && !(use_resident && cache->has_groups && cache->d_xforms)) return PM_ERR_INVALID;
     if (use_resident) {
         if (!cache->resident) return PM_ERR_INVALID;
         n_paths = cache->n_paths;
@@ -673,6 +754,7 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         }
         if (expect != ne) return PM_ERR_INVALID;
         cache->resident = false;
+        cache->has_groups = false;  // (decision D16: the map belongs to the paths it was given for)
         cache->has_outline = false;
         for (size_t p = 0; p < n_paths; ++p) {
             const uint32_t fl = h_paths[p].flags;
@@ -768,7 +850,11 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         PM_HIP_TRY(hipMemsetAsync(d_totals, 0, 8 * sizeof(uint32_t), stream));
         const uint32_t tb = 256;
         const uint32_t cap32 = static_cast<uint32_t>(std::min<size_t>(scene_cap, 0xffffffffull));
-        hipLaunchKernelGGL(KCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_move, d_err, d_pts64);
+        const GroupTable gt{cache->d_groups, cache->d_xforms};  // (read by the grouped forms only)
+        if (grouped)
+            hipLaunchKernelGGL(KCountGrouped, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, gt, el_npts, el_move, d_err, d_pts64);
+        else
+            hipLaunchKernelGGL(KCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_move, d_err, d_pts64);
         if (ne <= ScanSplit()) {
             hipLaunchKernelGGL(KScan, dim3(1), dim3(kScanThreads), 0, stream, d_paths, np, ne, el_npts, el_move, el_ptoff, el_mvoff,
                                path_item_base, path_pt_base, d_totals);
@@ -786,13 +872,23 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
                                path_pt_base, tops_p);
         }
         hipLaunchKernelGGL(KHeader, dim3(1), dim3(1), 0, stream, d_scene, static_cast<const uint32_t *>(d_totals), 0u, cap32);
-        hipLaunchKernelGGL(KPoints, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_ptoff,
-                           el_mvoff, path_pt_base, static_cast<const uint32_t *>(d_totals), static_cast<const unsigned long long *>(d_pts64), d_scene, cap32, d_bbox,
-                           sub_first);
+        if (grouped)
+            hipLaunchKernelGGL(KPointsGrouped, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, gt, el_npts, el_ptoff,
+                               el_mvoff, path_pt_base, static_cast<const uint32_t *>(d_totals), static_cast<const unsigned long long *>(d_pts64), d_scene, cap32,
+                               d_bbox, sub_first);
+        else
+            hipLaunchKernelGGL(KPoints, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, ne, aff, el_npts, el_ptoff,
+                               el_mvoff, path_pt_base, static_cast<const uint32_t *>(d_totals), static_cast<const unsigned long long *>(d_pts64), d_scene, cap32, d_bbox,
+                               sub_first);
         // (a wave per sub-path; sub-paths <= elements)
-        hipLaunchKernelGGL(KItems, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_npts, el_ptoff,
-                           el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals),
-                           static_cast<const unsigned long long *>(d_pts64), d_scene, cap32);
+        if (grouped)
+            hipLaunchKernelGGL(KItemsGrouped, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, gt, el_npts, el_ptoff,
+                               el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals),
+                               static_cast<const unsigned long long *>(d_pts64), d_scene, cap32);
+        else
+            hipLaunchKernelGGL(KItems, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_npts, el_ptoff,
+                               el_mvoff, path_item_base, path_pt_base, sub_first, d_bbox, static_cast<const uint32_t *>(d_totals),
+                               static_cast<const unsigned long long *>(d_pts64), d_scene, cap32);
         if (cache->has_outline) {
             // Styled strokes (decision D14): their poly-line items become outline Fill items, the outlines behind the end of the
             // scene as it stands.  KOutlineScan adds their entries to the 64-bit point sum: the host below sizes the scene by it.
@@ -806,20 +902,41 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
             const uint32_t *path_dash = has_dash ? cache->d_dash + 4 * cache->n_dashes : nullptr;
             const float *d_dash_values = has_dash ? reinterpret_cast<const float *>(cache->d_dash + 4 * cache->n_dashes + np) : nullptr;
             PM_HIP_TRY(hipMemsetAsync(d_out64, 0, 2 * sizeof(unsigned long long), stream));
-            hipLaunchKernelGGL(KOutlineCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
-                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), path_dash, out_cnt, d_out64);
-            if (has_dash)
+            if (grouped)
+                hipLaunchKernelGGL(KOutlineCountGrouped, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, gt, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), path_dash, out_cnt, d_out64);
+            else
+                hipLaunchKernelGGL(KOutlineCount, dim3((ne + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals), path_dash, out_cnt, d_out64);
+            if (has_dash && grouped)
+                hipLaunchKernelGGL(KDashCountGrouped, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, gt, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), path_dash, d_dashes, d_dash_values,
+                                   static_cast<const uint8_t *>(d_scene), cap32, out_cnt, d_out64);
+            else if (has_dash)
                 hipLaunchKernelGGL(KDashCount, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
                                    path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
                                    static_cast<const unsigned long long *>(d_pts64), path_dash, d_dashes, d_dash_values,
                                    static_cast<const uint8_t *>(d_scene), cap32, out_cnt, d_out64);
             hipLaunchKernelGGL(KOutlineScan, dim3(1), dim3(kScanThreads), 0, stream, static_cast<const uint32_t *>(d_totals),
                                static_cast<const uint32_t *>(out_cnt), out_off, d_out64, d_pts64);
-            hipLaunchKernelGGL(KOutline, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
-                               path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
-                               static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_off),
-                               static_cast<const unsigned long long *>(d_out64), path_dash, d_scene, cap32);
-            if (has_dash)
+            if (grouped)
+                hipLaunchKernelGGL(KOutlineGrouped, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, gt, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_off),
+                                   static_cast<const unsigned long long *>(d_out64), path_dash, d_scene, cap32);
+            else
+                hipLaunchKernelGGL(KOutline, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_off),
+                                   static_cast<const unsigned long long *>(d_out64), path_dash, d_scene, cap32);
+            if (has_dash && grouped)
+                hipLaunchKernelGGL(KDashGrouped, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, gt, el_ptoff, el_mvoff,
+                                   path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
+                                   static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_cnt),
+                                   static_cast<const uint32_t *>(out_off), static_cast<const unsigned long long *>(d_out64), path_dash, d_dashes,
+                                   d_dash_values, d_scene, cap32);
+            else if (has_dash)
                 hipLaunchKernelGGL(KDash, dim3((ne * 64u + tb - 1) / tb), dim3(tb), 0, stream, d_paths, np, d_els, width_scale, el_ptoff, el_mvoff,
                                    path_item_base, path_pt_base, sub_first, static_cast<const uint32_t *>(d_totals),
                                    static_cast<const unsigned long long *>(d_pts64), static_cast<const uint32_t *>(out_cnt),
@@ -859,6 +976,47 @@ fail:
         return PM_ERR_HIP;
     }
     return status;
+}
+
+int FlattenSetPathGroups(hipStream_t stream, FlattenCache *cache, const uint32_t *group_of_path, size_t n_paths, hipError_t *hip_error) {
+    if (!cache->resident || n_paths != cache->n_paths || !group_of_path) return PM_ERR_INVALID;
+    hipError_t e = Grow(&cache->d_groups, &cache->cap_groups, std::max<size_t>(n_paths, 1));
+    if (e == hipSuccess && n_paths) e = hipMemcpyAsync(cache->d_groups, group_of_path, n_paths * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) {
+        cache->has_groups = false;
+        if (hip_error) *hip_error = e;
+        return PM_ERR_HIP;
+    }
+    uint32_t mx = 0;
+    for (size_t p = 0; p < n_paths; ++p) mx = std::max(mx, group_of_path[p]);
+    cache->max_group = mx;
+    cache->has_groups = true;
+    return PM_OK;
+}
+
+int FlattenStageGroupTable(hipStream_t stream, FlattenCache *cache, const pm_group_xform *xforms, size_t n_groups, hipError_t *hip_error) {
+    hipError_t e = hipSuccess;
+    if (n_groups > cache->cap_xforms || !cache->d_xforms || !cache->h_xforms) {
+        // (nothing on the device reads the old table: every flatten call ends with its stream waited for)
+        if (cache->d_xforms) (void)hipFree(cache->d_xforms);
+        if (cache->h_xforms) (void)hipHostFree(cache->h_xforms);
+        cache->d_xforms = cache->h_xforms = nullptr;
+        cache->cap_xforms = 0;
+        const size_t want = n_groups + (n_groups >> 2) + 16;
+        e = hipMalloc(&cache->d_xforms, want * sizeof(pm_group_xform));
+        if (e == hipSuccess) e = hipHostMalloc(&cache->h_xforms, want * sizeof(pm_group_xform), hipHostMallocDefault);
+        if (e == hipSuccess) cache->cap_xforms = want;
+    }
+    if (e == hipSuccess) {
+        std::memcpy(cache->h_xforms, xforms, n_groups * sizeof(pm_group_xform));
+        e = hipMemcpyAsync(cache->d_xforms, cache->h_xforms, n_groups * sizeof(pm_group_xform), hipMemcpyHostToDevice, stream);
+    }
+    if (e != hipSuccess) {
+        if (hip_error) *hip_error = e;
+        return PM_ERR_HIP;
+    }
+    return PM_OK;
 }
 
 int FlattenPathItemBases(hipStream_t stream, const FlattenCache *cache, uint32_t *h_base, hipError_t *hip_error) {

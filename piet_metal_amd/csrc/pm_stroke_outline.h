@@ -98,8 +98,9 @@ struct OutlineJob {
     double mlim;
 };
 
-__device__ __forceinline__ OutlineJob MakeOutlineJob(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale,
-                                                     const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+template <bool kGrouped>
+__device__ __forceinline__ OutlineJob MakeOutlineJob(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale_u,
+                                                     const GroupTable &gt, const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
                                                      const uint32_t *path_pt_base, const uint32_t *sub_first_el, uint32_t n_items, uint32_t s) {
     OutlineJob job;
     const uint32_t first = sub_first_el[s];
@@ -121,6 +122,7 @@ __device__ __forceinline__ OutlineJob MakeOutlineJob(const pm_path *paths, uint3
     job.closed = els[last - 1u].tag == PM_EL_CLOSE;
     job.item = path_item_base[p] + (has_fill ? (compound ? 1u : n_sub_path) : 0u) + j;
     job.pts_ix = points_start + 8 * (static_cast<size_t>(path_pt_base[p]) + (has_fill ? path_pts + (compound ? n_sub_path : 0u) : 0u) + local);
+    const float width_scale = WidthScaleOf<kGrouped>(width_scale_u, gt, p);  // (decision D16: the path's own group's)
     float width = path.stroke_width * width_scale;
     job.rgba = path.stroke_rgba;
     ThinLine(&width, &job.rgba);
@@ -154,14 +156,15 @@ constexpr uint32_t kNoDash = 0xffffffffu;
 __device__ __forceinline__ bool IsDashed(const uint32_t *path_dash, uint32_t p) { return path_dash != nullptr && path_dash[p] != kNoDash; }
 
 // One thread per sub-path: out_cnt[s] = entries of its outline (0: not a styled stroke); their 64-bit sum to *out_total.
-__global__ void KOutlineCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
-                              const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
-                              const uint32_t *sub_first_el, const uint32_t *totals, const uint32_t *path_dash, uint32_t *out_cnt,
-                              unsigned long long *out_total) {
+template <bool kGrouped>
+__device__ __forceinline__ void OutlineCountBody(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const GroupTable &gt,
+                                                 const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+                                                 const uint32_t *path_pt_base, const uint32_t *sub_first_el, const uint32_t *totals,
+                                                 const uint32_t *path_dash, uint32_t *out_cnt, unsigned long long *out_total) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned long long q = 0;
     if (s < totals[2]) {
-        const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals[0], s);
+        const OutlineJob job = MakeOutlineJob<kGrouped>(paths, n_paths, els, width_scale, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals[0], s);
         const bool dashed = job.styled && IsDashed(path_dash, job.path);
         if (job.styled && !dashed) q = LayoutOf(job).total;
         if (!dashed) out_cnt[s] = static_cast<uint32_t>(q);  // (a count past 2^32 never fits: the 64-bit sum says so, KOutline then writes nothing)
@@ -169,6 +172,22 @@ __global__ void KOutlineCount(const pm_path *paths, uint32_t n_paths, const pm_p
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) q += __shfl_xor(q, d, 64);
     if ((threadIdx.x & 63u) == 0 && q != 0) atomicAdd(out_total, q);
+}
+
+__global__ void KOutlineCount(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
+                              const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
+                              const uint32_t *sub_first_el, const uint32_t *totals, const uint32_t *path_dash, uint32_t *out_cnt,
+                              unsigned long long *out_total) {
+    OutlineCountBody<false>(paths, n_paths, els, width_scale, GroupTable{nullptr, nullptr}, el_ptoff, el_mvoff, path_item_base, path_pt_base,
+                            sub_first_el, totals, path_dash, out_cnt, out_total);
+}
+
+__global__ void KOutlineCountGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, GroupTable gt, const uint32_t *el_ptoff,
+                                     const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base,
+                                     const uint32_t *sub_first_el, const uint32_t *totals, const uint32_t *path_dash, uint32_t *out_cnt,
+                                     unsigned long long *out_total) {
+    OutlineCountBody<true>(paths, n_paths, els, 0.0f, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals, path_dash, out_cnt,
+                           out_total);
 }
 
 // One workgroup: exclusive scan of out_cnt over the sub-paths.  Then the scene's 64-bit point count grows by the outlines'
@@ -414,15 +433,17 @@ __device__ __forceinline__ void WriteOutlineItem(uint8_t *scene, uint32_t scene_
 }
 
 // One WAVE per sub-path, as in KItems.
-__global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
-                         const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
-                         const uint32_t *totals, const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
-                         const uint32_t *path_dash, uint8_t *scene, uint32_t scene_cap) {
+template <bool kGrouped>
+__device__ __forceinline__ void OutlineBody(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const GroupTable &gt,
+                                            const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+                                            const uint32_t *path_pt_base, const uint32_t *sub_first_el, const uint32_t *totals,
+                                            const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
+                                            const uint32_t *path_dash, uint8_t *scene, uint32_t scene_cap) {
     const uint32_t s = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t n_items = totals[0], n_subs = totals[2];
     if (s >= n_subs || Overfull(n_items, *n_pts64, scene_cap)) return;  // (whole waves; *n_pts64 counts the outlines by now)
-    const OutlineJob job = MakeOutlineJob(paths, n_paths, els, width_scale, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
+    const OutlineJob job = MakeOutlineJob<kGrouped>(paths, n_paths, els, width_scale, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, n_items, s);
     if (!job.styled || IsDashed(path_dash, job.path)) return;  // (uniform)
     const OutlineLayout lay = LayoutOf(job);
     const size_t outlines_start = sizeof(SimpleGroup) + static_cast<size_t>(n_items) * (sizeof(ShortBbox) + kItemSize) + 8 * static_cast<size_t>(out_total[1]);
@@ -430,4 +451,21 @@ __global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n
     OutlineSink sink{scene, outlines_start + 8 * static_cast<size_t>(out_off[s]), scene_cap, nan, nan, nan, nan, false};
     OutlineSubpath(scene, job, lay, sink, lane);
     WriteOutlineItem(scene, scene_cap, n_items, job, sink, static_cast<uint32_t>(lay.total), lane);
+}
+
+__global__ __launch_bounds__(256) void KOutline(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, float width_scale, const uint32_t *el_ptoff,
+                         const uint32_t *el_mvoff, const uint32_t *path_item_base, const uint32_t *path_pt_base, const uint32_t *sub_first_el,
+                         const uint32_t *totals, const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
+                         const uint32_t *path_dash, uint8_t *scene, uint32_t scene_cap) {
+    OutlineBody<false>(paths, n_paths, els, width_scale, GroupTable{nullptr, nullptr}, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el,
+                       totals, n_pts64, out_off, out_total, path_dash, scene, scene_cap);
+}
+
+__global__ __launch_bounds__(256) void KOutlineGrouped(const pm_path *paths, uint32_t n_paths, const pm_path_el *els, GroupTable gt,
+                                                       const uint32_t *el_ptoff, const uint32_t *el_mvoff, const uint32_t *path_item_base,
+                                                       const uint32_t *path_pt_base, const uint32_t *sub_first_el, const uint32_t *totals,
+                                                       const unsigned long long *n_pts64, const uint32_t *out_off, const unsigned long long *out_total,
+                                                       const uint32_t *path_dash, uint8_t *scene, uint32_t scene_cap) {
+    OutlineBody<true>(paths, n_paths, els, 0.0f, gt, el_ptoff, el_mvoff, path_item_base, path_pt_base, sub_first_el, totals, n_pts64, out_off,
+                      out_total, path_dash, scene, scene_cap);
 }

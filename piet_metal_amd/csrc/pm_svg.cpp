@@ -48,6 +48,9 @@ struct pm_svg {
     std::vector<pm_path_el> els;
     std::vector<pm_path_dash> dashes;  // with PM_SVG_STROKE_DASHES: the dash table (decision D15), ascending by path
     std::vector<float> dash_values;
+    // per path: which element child of the outermost <svg> drew it (its ordinal among them; a <use>: the child where it stands) --
+    // the top-level groups an application animates (decision D16, pm_path_groups)
+    std::vector<uint32_t> groups;
     // the outermost <svg>: viewBox (if any), width / height in user units (0: absent or a percentage)
     bool has_viewbox = false, seen_root = false;
     double viewbox[4] = {0, 0, 0, 0};
@@ -1029,6 +1032,10 @@ struct Doc {
     int flags;
     pm_svg *out;
     uint64_t use_expansions = 0;
+    // the element children of the outermost <svg> (of the document itself while none was seen): the depth they open at, how many
+    // were met, and the one the walk is inside of
+    size_t child_depth = 0;
+    uint32_t n_children = 0, cur_child = 0;
     std::vector<IdRange> ids;
     std::vector<CssRule> css;
 };
@@ -1171,6 +1178,7 @@ int ParseRange(Doc *doc, const char *text, const char *end, const Style &initial
         const bool skipped = (name_len == 4 && std::memcmp(n0, "defs", 4) == 0) || (name_len == 8 && std::memcmp(n0, "clipPath", 8) == 0) ||
                              (name_len == 4 && std::memcmp(n0, "mask", 4) == 0) || (is_symbol && !(use_depth > 0 && lt == text)) ||
                              (name_len == 7 && std::memcmp(n0, "pattern", 7) == 0) || (name_len == 6 && std::memcmp(n0, "marker", 6) == 0);
+        if (use_depth == 0 && container.size() == doc->child_depth) doc->cur_child = doc->n_children++;
         if (skipped && !self_closing) {
             // definitions are not rendered directly: skip to the matching end tag
             const std::string close = "</" + std::string(n0, name_len);
@@ -1222,6 +1230,10 @@ int ParseRange(Doc *doc, const char *text, const char *end, const Style &initial
             if (!ScanAttrs(p, q, &attrs)) return PM_ERR_PARSE;
             if (name_len == 3 && n0[0] == 's' && !out->seen_root) {  // the outermost <svg>: where the picture lives
                 out->seen_root = true;
+                if (use_depth == 0) {  // its element children are counted from here
+                    doc->child_depth = container.size() + 1;
+                    doc->n_children = doc->cur_child = 0;
+                }
                 auto length = [](const Attr *a) -> double {  // user units / px; a percentage has no meaning here
                     if (!a) return 0.0;
                     const std::string v(a->val, a->val_len);
@@ -1311,8 +1323,12 @@ int ParseRange(Doc *doc, const char *text, const char *end, const Style &initial
                             for (float v : st.dash) out->dash_values.push_back(scaled(v));
                         }
                     }
-                    if (path.flags & (PM_PATH_FILL | PM_PATH_STROKE)) out->paths.push_back(path);
-                    else out->els.resize(el0);
+                    if (path.flags & (PM_PATH_FILL | PM_PATH_STROKE)) {
+                        out->paths.push_back(path);
+                        out->groups.push_back(doc->cur_child);
+                    } else {
+                        out->els.resize(el0);
+                    }
                 }
                 if (!self_closing) container.push_back(false);
             }
@@ -1399,6 +1415,7 @@ const pm_path_dash *pm_svg_dashes(const pm_svg *s) { return s ? s->dashes.data()
 size_t pm_svg_n_dashes(const pm_svg *s) { return s ? s->dashes.size() : 0; }
 const float *pm_svg_dash_values(const pm_svg *s) { return s ? s->dash_values.data() : nullptr; }
 size_t pm_svg_n_dash_values(const pm_svg *s) { return s ? s->dash_values.size() : 0; }
+const uint32_t *pm_svg_path_groups(const pm_svg *s) { return s ? s->groups.data() : nullptr; }
 int pm_svg_viewbox(const pm_svg *s, double viewbox[4], double *width, double *height) {
     if (!s) return 0;
     if (viewbox) std::memcpy(viewbox, s->viewbox, sizeof(s->viewbox));

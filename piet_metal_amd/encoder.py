@@ -165,28 +165,49 @@ def _dash_arrays(table: dict):
 class PathSet:
     """Parsed paths: `paths` (structured, 24 B) and `els` (structured, 56 B) arrays
     in the layout of pm_path / pm_path_el; optionally a dash table (decision D15): `dashes`
-    (structured, 16 B, pm_path_dash, ascending by path) and the f32 `dash_values` they index."""
+    (structured, 16 B, pm_path_dash, ascending by path) and the f32 `dash_values` they index; optionally `groups` (decision D16):
+    a uint32 group index per path, what Renderer.reflatten_groups moves together (None: no map; the set counts as one group)."""
 
     PATH_DTYPE = _PATH_DTYPE
     EL_DTYPE = _EL_DTYPE
     DASH_DTYPE = _DASH_DTYPE
 
-    def __init__(self, paths: np.ndarray, els: np.ndarray, dashes: np.ndarray | None = None, dash_values: np.ndarray | None = None):
+    def __init__(self, paths: np.ndarray, els: np.ndarray, dashes: np.ndarray | None = None, dash_values: np.ndarray | None = None,
+                 groups: np.ndarray | None = None):
         self.paths = np.ascontiguousarray(paths, dtype=_PATH_DTYPE)
         self.els = np.ascontiguousarray(els, dtype=_EL_DTYPE)
         self.dashes = np.ascontiguousarray(dashes if dashes is not None else np.zeros(0, _DASH_DTYPE), dtype=_DASH_DTYPE)
         self.dash_values = np.ascontiguousarray(dash_values if dash_values is not None else np.zeros(0, np.float32), dtype=np.float32)
+        self.groups = None if groups is None else self._checked_groups(groups, len(self.paths))
+
+    @staticmethod
+    def _checked_groups(groups, n_paths: int) -> np.ndarray:
+        g = np.asarray(groups)
+        if g.shape != (n_paths,) or (g.size and not (np.issubdtype(g.dtype, np.integer) and g.min() >= 0 and g.max() <= 0xFFFFFFFF)):
+            raise ValueError("groups is one uint32 group index per path")
+        return np.ascontiguousarray(g, dtype=np.uint32)
+
+    def n_groups(self) -> int:
+        """Groups the set's map names (largest index + 1); a set without a map, or without paths, counts as one group."""
+        return int(self.groups.max()) + 1 if self.groups is not None and len(self.groups) else 1
+
+    def with_groups(self, groups) -> "PathSet":
+        """A copy with this group map (decision D16): a uint32 group index per path, or None for no map."""
+        out = self._like(self.paths, self.els)
+        out.groups = None if groups is None else self._checked_groups(groups, len(self.paths))
+        return out
 
     def _like(self, paths, els, dashes=None, dash_values=None) -> "PathSet":
-        """A set of these arrays that keeps this one's dash table (unless given) and document attributes."""
-        out = PathSet(paths, els, self.dashes if dashes is None else dashes, self.dash_values if dash_values is None else dash_values)
+        """A set of these arrays that keeps this one's dash table (unless given), group map and document attributes."""
+        out = PathSet(paths, els, self.dashes if dashes is None else dashes, self.dash_values if dash_values is None else dash_values,
+                      self.groups)
         for k in ("viewbox", "size"):
             if hasattr(self, k):
                 setattr(out, k, getattr(self, k))
         return out
 
     @classmethod
-    def _from_handle(cls, lib, h) -> "PathSet":
+    def _from_handle(cls, lib, h, groups: bool = False) -> "PathSet":
         try:
             npaths, nels = lib.pm_svg_n_paths(h), lib.pm_svg_n_els(h)
             paths = np.frombuffer(C.string_at(lib.pm_svg_paths(h), npaths * 24), dtype=_PATH_DTYPE).copy() if npaths else np.zeros(0, _PATH_DTYPE)
@@ -194,11 +215,14 @@ class PathSet:
             ndash, nval = lib.pm_svg_n_dashes(h), lib.pm_svg_n_dash_values(h)
             dashes = np.frombuffer(C.string_at(lib.pm_svg_dashes(h), ndash * 16), dtype=_DASH_DTYPE).copy() if ndash else None
             values = np.frombuffer(C.string_at(lib.pm_svg_dash_values(h), nval * 4), dtype=np.float32).copy() if nval else None
+            gmap = None
+            if groups:
+                gmap = np.frombuffer(C.string_at(lib.pm_svg_path_groups(h), npaths * 4), dtype=np.uint32).copy() if npaths else np.zeros(0, np.uint32)
             vb, w, hh = (C.c_double * 4)(), C.c_double(0), C.c_double(0)
             has_vb = lib.pm_svg_viewbox(h, vb, C.byref(w), C.byref(hh))
         finally:
             lib.pm_svg_free(h)
-        ps = cls(paths, els, dashes, values)
+        ps = cls(paths, els, dashes, values, gmap)
         ps.viewbox = tuple(vb) if has_vb else None  # the outermost <svg>'s viewBox (user units)
         ps.size = (w.value, hh.value)                # its width / height in px (0: not given)
         return ps
@@ -218,13 +242,15 @@ class PathSet:
 
     @classmethod
     def from_svg(cls, text: bytes | str, reject_arc_paths: bool = False, spec_defaults: bool = False, flat_gradients: bool = False,
-                 stroke_styles: bool = False, stroke_dashes: bool = False) -> "PathSet":
+                 stroke_styles: bool = False, stroke_dashes: bool = False, groups: bool = False) -> "PathSet":
         """Parse an SVG document.  spec_defaults: SVG's initial `fill: black` instead of the
         reference's rule that only a fill property fills (src/lib.rs:299); flat_gradients: a
         url(#gradient) paint becomes the mean colour of the gradient's stops instead of `none`;
         stroke_styles: stroke-linecap / stroke-linejoin / stroke-miterlimit are read and every stroke
         is drawn as its outline (decision D14) instead of the round poly-line; stroke_dashes (needs
-        stroke_styles): stroke-dasharray / stroke-dashoffset are read into the dash table (decision D15)."""
+        stroke_styles): stroke-dasharray / stroke-dashoffset are read into the dash table (decision D15); groups: `groups` is filled
+        with the document's top-level groups (decision D16) -- for every path the ordinal, among the element children of the
+        outermost <svg>, of the child that drew it (a <use>: the child where it stands)."""
         lib = _lib.load()
         data = text.encode() if isinstance(text, str) else bytes(text)
         err = C.c_int(0)
@@ -235,17 +261,17 @@ class PathSet:
         h = lib.pm_svg_parse(data, len(data), flags, C.byref(err))
         if not h:
             raise _lib.PietMetalError(err.value, "pm_svg_parse")
-        return cls._from_handle(lib, h)
+        return cls._from_handle(lib, h, groups)
 
     @classmethod
-    def tiger(cls, reject_arc_paths: bool = False) -> "PathSet":
-        """The embedded Ghostscript_Tiger.svg (src/lib.rs:288)."""
+    def tiger(cls, reject_arc_paths: bool = False, groups: bool = False) -> "PathSet":
+        """The embedded Ghostscript_Tiger.svg (src/lib.rs:288); groups as in from_svg."""
         lib = _lib.load()
         err = C.c_int(0)
         h = lib.pm_svg_tiger(_lib.PM_SVG_REJECT_ARC_PATHS if reject_arc_paths else 0, C.byref(err))
         if not h:
             raise _lib.PietMetalError(err.value, "pm_svg_tiger")
-        return cls._from_handle(lib, h)
+        return cls._from_handle(lib, h, groups)
 
     CAPS = {"butt": _lib.PM_STROKE_CAP_BUTT, "round": _lib.PM_STROKE_CAP_ROUND, "square": _lib.PM_STROKE_CAP_SQUARE}
     JOINS = {"miter": _lib.PM_STROKE_JOIN_MITER, "round": _lib.PM_STROKE_JOIN_ROUND, "bevel": _lib.PM_STROKE_JOIN_BEVEL}
@@ -286,13 +312,17 @@ class PathSet:
     def fills_only(self) -> "PathSet":
         p = self.paths.copy()
         p["flags"] &= _lib.PM_PATH_FILL
-        return PathSet(p, self.els)
+        return PathSet(p, self.els, groups=self.groups)
 
     @staticmethod
     def concat(sets: list["PathSet"]) -> "PathSet":
         paths, els, base = [], [], 0
         dashes, values, pbase, vbase = [], [], 0, 0
+        # group maps (decision D16): every set's indices behind those of the sets before it; a set without a map is one group
+        groups, gbase, any_groups = [], 0, any(s.groups is not None for s in sets)
         for s in sets:
+            groups.append((s.groups if s.groups is not None else np.zeros(len(s.paths), np.uint32)).astype(np.uint64) + gbase)
+            gbase += s.n_groups()
             p = s.paths.copy()
             p["el_begin"] += base
             p["el_end"] += base
@@ -306,7 +336,8 @@ class PathSet:
             vbase += len(s.dash_values)
             dashes.append(d)
             values.append(s.dash_values)
-        return PathSet(np.concatenate(paths), np.concatenate(els), np.concatenate(dashes), np.concatenate(values))
+        return PathSet(np.concatenate(paths), np.concatenate(els), np.concatenate(dashes), np.concatenate(values),
+                       np.concatenate(groups) if any_groups else None)
 
     def transformed(self, affine) -> "PathSet":
         """Apply an affine [a b c d e f] to the element coordinates on the host
@@ -317,4 +348,4 @@ class PathSet:
         x, y = p[:, 0::2].copy(), p[:, 1::2].copy()
         p[:, 0::2] = a * x + c * y + e
         p[:, 1::2] = b * x + d * y + f
-        return PathSet(self.paths, els, self.dashes, self.dash_values)  # (dash lengths are in user units: width_scale scales them)
+        return PathSet(self.paths, els, self.dashes, self.dash_values, self.groups)  # (dash lengths are in user units: width_scale scales them)

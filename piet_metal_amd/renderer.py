@@ -109,14 +109,46 @@ class Renderer:
                 ),
                 "pm_flatten_and_encode_dashed",
             )
-            return nbytes.value, nitems.value
-        _lib.check(
-            self._lib.pm_flatten_and_encode(
-                self._h, paths.paths.ctypes.data, len(paths.paths), paths.els.ctypes.data, len(paths.els), aff,
-                float(width_scale), C.byref(nbytes), C.byref(nitems),
-            ),
-            "pm_flatten_and_encode",
-        )
+        else:
+            _lib.check(
+                self._lib.pm_flatten_and_encode(
+                    self._h, paths.paths.ctypes.data, len(paths.paths), paths.els.ctypes.data, len(paths.els), aff,
+                    float(width_scale), C.byref(nbytes), C.byref(nitems),
+                ),
+                "pm_flatten_and_encode",
+            )
+        if getattr(paths, "groups", None) is not None:
+            self.set_path_groups(paths.groups)
+        return nbytes.value, nitems.value
+
+    def set_path_groups(self, groups) -> None:
+        """Give every resident path its group index (decision D16): what reflatten_groups moves together.  The map stays with
+        the resident paths until the next flatten_and_encode."""
+        g = np.ascontiguousarray(groups, dtype=np.uint32)
+        if g.ndim != 1:
+            raise ValueError("groups is one uint32 group index per path")
+        _lib.check(self._lib.pm_path_groups(self._h, g.ctypes.data, len(g)), "pm_path_groups")
+
+    GROUP_XFORM_DTYPE = np.dtype([("m", "<f8", (6,)), ("width_scale", "<f4"), ("reserved", "<u4")])  # pm_group_xform
+
+    def reflatten_groups(self, affines, width_scales=None) -> tuple[int, int]:
+        """Re-flatten the resident paths with one transform per group (animating objects: no upload, no allocation):
+        affines is (G, 6) float64, [a b c d e f] per group; width_scales (G,) scales stroke widths and dash lengths per group,
+        by default sqrt|det| of each matrix, computed in float64 and rounded to f32.  Returns (scene_bytes, n_items)."""
+        a = np.asarray(affines, np.float64)
+        if a.ndim != 2 or a.shape[1] != 6:
+            raise ValueError("affines is a (G, 6) array")
+        if width_scales is None:
+            ws = np.sqrt(np.abs(a[:, 0] * a[:, 3] - a[:, 1] * a[:, 2])).astype(np.float32)
+        else:
+            ws = np.asarray(width_scales, np.float32).reshape(-1)
+            if ws.shape != (len(a),):
+                raise ValueError("width_scales is one value per group")
+        table = np.zeros(len(a), self.GROUP_XFORM_DTYPE)
+        table["m"] = a
+        table["width_scale"] = ws
+        nbytes, nitems = C.c_size_t(0), C.c_uint32(0)
+        _lib.check(self._lib.pm_reflatten_groups(self._h, table.ctypes.data, len(table), C.byref(nbytes), C.byref(nitems)), "pm_reflatten_groups")
         return nbytes.value, nitems.value
 
     def reflatten(self, affine, width_scale: float) -> tuple[int, int]:
