@@ -291,6 +291,30 @@ int pm_path_groups(pm_ctx *c, const uint32_t *group_of_path, size_t n_paths);
  * returns.  PM_ERR_INVALID: no resident paths or no resident map, a NULL pointer, n_groups == 0 or not above the largest index
  * of the map (a longer table is fine), a non-zero `reserved`. */
 int pm_reflatten_groups(pm_ctx *c, const pm_group_xform *xforms, size_t n_groups, size_t *scene_bytes, uint32_t *n_items);
+/* Fading and tinting groups of paths (decision D17): one paint per group of the resident map (pm_path_groups).
+ * Path p's fill_rgba and stroke_rgba, AS THE LAST pm_flatten_and_encode* GAVE THEM (paints do not accumulate), go through
+ * paints[group_of_path[p]], in integers, on the stored sRGB-encoded bytes:
+ *     R, G, B:  (c * (255 - k) + t * k + 127) / 255     k = the tint's AA byte, t = the tint's channel
+ *     A:        (a * opacity + 127) / 255               round to nearest, no tie (255 is odd); {0, 255} changes nothing
+ * The resident scene becomes, byte for byte, the scene D1-D16 define for the painted paths under the transform(s) of the call
+ * that made it: only the items' colour words change (the thin-line rule acts on the painted alpha; an outline or dashed item
+ * carries the painted, thin-lined stroke colour); length, *n_items, boxes, points, pm_item_paths and paint order stay.  Nothing is
+ * flattened, nothing read back, the scene index and the binning plan in force stay (pm_get_binning_plans does not move);
+ * pm_get_scene_timings reports the call's host time as flatten_encode_ms and scene_index_ms = 0.  As after every scene
+ * replacement, the frames rendered before the call are no longer "the last frame": pm_read_pixels / pm_framebuffer_device_ptr
+ * name a frame again once one of the painted scene has been rendered.
+ * This is no group compositing: an opacity multiplies every item's own alpha, as the SVG front-end folds `opacity` into the items;
+ * overlapping items of a faded group show through each other.
+ * The paint stays with the resident paths: a later pm_reflatten / pm_reflatten_groups flattens the painted paths;
+ * pm_flatten_and_encode* forgets it; pm_path_groups does not touch it (the colours change with the next paint).
+ * PM_ERR_INVALID, nothing changed: a NULL pointer, no resident paths, no resident map, n_groups == 0 or not above the largest
+ * index of the map (a longer table is fine), an opacity above 255, a resident scene that did not come from the resident paths
+ * (pm_upload_scene since, or the last replacement failed). */
+typedef struct {
+    uint32_t tint_rgba; /* 0xRRGGBBAA: RR GG BB = the colour mixed in, AA = how much of it (0 none, 255 all) */
+    uint32_t opacity;   /* 0..255, multiplies the alpha; above 255: PM_ERR_INVALID */
+} pm_group_paint;       /* 8 bytes; identity = {0, 255} */
+int pm_repaint_groups(pm_ctx *c, const pm_group_paint *paints, size_t n_groups);
 /* pm_flatten_and_encode with a dash table (decision D15): the styled stroke of every path named in `dashes` is cut into dashes
  * on the device.  A dashed stroke stays ONE compound Fill item per sub-path in the poly-line's slot -- *n_items and pm_item_paths
  * do not change -- whose entries are the D14 outlines of its dashes.  `dashes` is strictly ascending by path; PM_ERR_INVALID: an

@@ -89,7 +89,11 @@ class GroupXform(C.Structure):  # pm_group_xform (decision D16): one group's aff
     _fields_ = [("m", C.c_double * 6), ("width_scale", C.c_float), ("reserved", C.c_uint32)]
 
 
-assert C.sizeof(PathEl) == 56 and C.sizeof(Path) == 24 and C.sizeof(Cmd) == 24 and C.sizeof(GroupXform) == 56
+class GroupPaint(C.Structure):  # pm_group_paint (decision D17): one group's tint (0xRRGGBBAA, AA = how much of it) and opacity (0..255)
+    _fields_ = [("tint_rgba", C.c_uint32), ("opacity", C.c_uint32)]
+
+
+assert C.sizeof(PathEl) == 56 and C.sizeof(Path) == 24 and C.sizeof(Cmd) == 24 and C.sizeof(GroupXform) == 56 and C.sizeof(GroupPaint) == 8
 
 # name -> (restype, argtypes); every symbol include/piet_metal_amd.h declares
 SIGNATURES = {
@@ -142,6 +146,7 @@ SIGNATURES = {
     "pm_reflatten": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.c_float, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
     "pm_path_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "pm_reflatten_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint32)]),
+    "pm_repaint_groups": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "pm_download_scene": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "pm_render": (C.c_int, [C.c_void_p]),
     "pm_render_to": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -5,6 +5,7 @@
 
     python -m piet_metal_amd.cli tiger spin.png --frames 60 --spin 360     (spin-000.png ... spin-059.png)
     python -m piet_metal_amd.cli drawing.svg apart.png --frames 30 --explode 1.5    (the top-level groups move apart)
+    python -m piet_metal_amd.cli drawing.svg gone.png --frames 30 --fade            (the top-level groups fade out one after another)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -14,7 +15,8 @@ transforms, style, opacity, fill-rule, basic shapes; SVG's initial `fill: black`
 embedded asset read as make_tiger reads it (src/lib.rs:286-328).  --frames renders an animation the
 way the reference's view does on every change (PietRenderer.m:90-101, :145): the scene is encoded
 again for each frame -- here by re-flattening the resident paths on the device (pm_reflatten; with
---explode pm_reflatten_groups, one affine per top-level group of the document).
+--explode pm_reflatten_groups, one affine per top-level group of the document).  --fade changes colours only: nothing is
+flattened again, pm_repaint_groups rewrites the colour words of the resident scene (one opacity per top-level group).
 """
 from __future__ import annotations
 
@@ -80,6 +82,7 @@ def main(argv=None) -> int:
     ap.add_argument("--frames", type=int, default=1, help="render an animation of this many frames (output NAME-###.png)")
     ap.add_argument("--spin", type=float, default=360.0, help="--frames: total rotation about the viewport centre, degrees")
     ap.add_argument("--explode", type=float, default=None, metavar="F", help="--frames N (>= 2): instead of spinning, frame k moves every top-level group of the document (element child of the outermost <svg>) by F * k / (N - 1) * (its centre - the document's centre); the groups are re-flattened on the device, each under its own affine")
+    ap.add_argument("--fade", action="store_true", help="--frames N (>= 2): instead of spinning, the top-level groups of the document fade out one after another: frame k shows group g of G with opacity round(255 * clamp(1 - k / (N - 1) * G + g, 0, 1)); only the colours of the resident scene are rewritten on the device.  With --explode: both")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
     args = ap.parse_args(argv)
     try:
@@ -90,16 +93,19 @@ def main(argv=None) -> int:
         ap.error("--pick takes X,Y")
     if args.explode is not None and args.frames < 2:
         ap.error("--explode needs --frames N with N >= 2")
+    if args.fade and args.frames < 2:
+        ap.error("--fade needs --frames N with N >= 2")
+    grouped = args.explode is not None or args.fade
 
     from . import PathSet, Renderer
 
     if args.input == "tiger":
-        paths = PathSet.tiger(args.reject_arc_paths, groups=args.explode is not None)
+        paths = PathSet.tiger(args.reject_arc_paths, groups=grouped)
     else:
         with open(args.input, "rb") as f:
             paths = PathSet.from_svg(f.read(), args.reject_arc_paths, spec_defaults=not args.reference_fill_rule, flat_gradients=not args.no_flat_gradients,
                                      stroke_styles=args.stroke_styles or args.stroke_dashes, stroke_dashes=args.stroke_dashes,
-                                     groups=args.explode is not None)
+                                     groups=grouped)
     scale = args.scale if args.scale is not None else args.height / 200.0
     off = args.offset if args.offset is not None else ((args.width - args.height) / 2.0 if args.scale is None else 0.0, 0.0)
     base = (scale, 0.0, 0.0, scale, float(off[0]), float(off[1]))
@@ -133,8 +139,10 @@ def main(argv=None) -> int:
             if away is not None:  # every top-level group under its own affine: base after a translation in user units
                 affs = explode_affines(base, away * (args.explode * k / (args.frames - 1)))
                 nbytes, nitems = r.reflatten_groups(affs, np.full(len(affs), scale, np.float32))
-            else:
+            elif not args.fade:
                 nbytes, nitems = r.reflatten(aff, scale)  # the per-frame re-encode, on the device
+            if args.fade:  # colours only: no flatten, the scene index and the binning plan stay
+                r.repaint_groups(fade_opacities(k, args.frames, paths.n_groups()))
             r.render()
             r.sync()
             t_gpu += time.perf_counter() - t0
@@ -166,6 +174,15 @@ def group_offsets(paths) -> np.ndarray:
         if c is not None:
             out[g] = c - doc
     return out
+
+
+def fade_opacities(k: int, n_frames: int, n_groups: int) -> np.ndarray:
+    """(G,) uint32: the opacity of every group in frame k of n_frames (>= 2): round(255 * clamp(1 - k / (N - 1) * G + g, 0, 1)),
+    in exact integer arithmetic.  All 255 in frame 0, all 0 in the last; group g is gone when group g + 1 begins to fade."""
+    g = np.arange(n_groups, dtype=np.int64)
+    den = n_frames - 1
+    num = np.clip(den * (1 + g) - k * n_groups, 0, den)  # clamp(...) * den
+    return ((2 * 255 * num + den) // (2 * den)).astype(np.uint32)
 
 
 def explode_affines(base, shifts) -> np.ndarray:

@@ -242,7 +242,11 @@ struct pm_ctx {
     size_t user_scene_bytes = 0;  // what the caller uploaded / the flatten kernels wrote
     uint32_t dev_bbox_ix = 8, dev_items_ix = 0;  // the drawn group's ShortBbox / item arrays in d_scene
     uint32_t n_items = 0;
-    std::vector<uint8_t> item_meta;  // copy of header + bboxes + items (arena sizing)
+    // copy of header + bboxes + items (arena sizing).  After pm_repaint_groups (decision D17) it is not refreshed: the records are
+    // geometry-valid and colour-stale (meta_colours_stale).  The host reads tags, point counts, point offsets and boxes from it,
+    // never a colour; pm_fill_coverage, which hands a record back to the device, then fetches that record from the scene.
+    std::vector<uint8_t> item_meta;
+    bool meta_colours_stale = false;
     std::vector<uint32_t> chunk_base_host;  // source of the asynchronous upload of the chunk table
     std::vector<uint64_t> stage_need_diff;  // StripRowBounds' scratch
     std::vector<uint4> stage_desc;          // ... of the strip-row work list,
@@ -1470,6 +1474,7 @@ void InvalidateScene(pm_ctx *c) {
     c->n_items = 0;
     c->n_chunks = 0;
     c->item_meta.clear();
+    c->meta_colours_stale = false;
     c->scene_from_paths = false;
     c->last_slot = -1;
     c->arena_dirty = true;
@@ -1595,6 +1600,7 @@ int SetScene(pm_ctx *c, size_t bytes, const uint8_t *host) {
         return r;
     }
     c->item_meta.swap(meta);
+    c->meta_colours_stale = false;
     c->n_items = n;
     c->dev_bbox_ix = dev_bbox_ix;
     c->dev_items_ix = dev_items_ix;
@@ -2161,10 +2167,77 @@ int pm_reflatten_groups(pm_ctx *c, const pm_group_xform *xforms, size_t n_groups
     PM_TRY(hipSetDevice(c->device));
     hipError_t he = hipSuccess;
     // (the one copy of the table, in front of the kernels; a grow-and-retry finds it where it is)
-    if (pm::FlattenStageGroupTable(c->stream, &c->flatten_cache, xforms, n_groups, &he) != PM_OK) return HipFail(he, "pm_reflatten_groups");
+    if (pm::FlattenStageGroupTable(c->stream, &c->flatten_cache, xforms, n_groups, &he) != PM_OK) {
+        // (the table of the resident scene may be gone with the failed re-allocation: a grouped scene without its table cannot be
+        //  repainted, decision D17 -- whatever happened, the old scene is gone, as after any failed replacement)
+        (void)SyncAll(c);
+        InvalidateScene(c);
+        return HipFail(he, "pm_reflatten_groups");
+    }
     c->replan_wide = true;  // (as pm_reflatten: the next plan is made to last, EnsureArena)
     const double unused[6] = {1.0, 0.0, 0.0, 1.0, 0.0, 0.0};
     return FlattenAndEncode(c, true, nullptr, 0, nullptr, 0, nullptr, unused, 1.0f, scene_bytes, n_items, true);
+}
+
+// Decision D17: the colours of the resident scene change, nothing else.  No flatten kernel, no read-back, no SetScene, no scene
+// index (it is geometry only), and the binning plan in force stays (arena_dirty is left alone): the next frame bins the same boxes
+// into the same regions.  The kernels write the OTHER scene buffer, as FlattenAndEncode's do, and the two change places.
+int pm_repaint_groups(pm_ctx *c, const pm_group_paint *paints, size_t n_groups) {
+    if (!c || !paints) {
+        SetError("pm_repaint_groups: NULL argument");
+        return PM_ERR_INVALID;
+    }
+    const pm::FlattenCache &fc = c->flatten_cache;
+    if (!fc.resident) {
+        SetError("pm_repaint_groups: no paths resident (pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    if (!fc.has_groups) {
+        SetError("pm_repaint_groups: no group map resident (pm_path_groups after pm_flatten_and_encode)");
+        return PM_ERR_INVALID;
+    }
+    if (n_groups == 0 || n_groups <= fc.max_group) {
+        SetError("pm_repaint_groups: " + std::to_string(n_groups) + " paints for a group map that reaches index " + std::to_string(fc.max_group));
+        return PM_ERR_INVALID;
+    }
+    for (size_t g = 0; g < n_groups; ++g) {
+        if (paints[g].opacity > 255u) {
+            SetError("pm_repaint_groups: opacity " + std::to_string(paints[g].opacity) + " is above 255 (paint " + std::to_string(g) + ")");
+            return PM_ERR_INVALID;
+        }
+    }
+    if (!c->scene_from_paths || c->scene_bytes < 8 || c->scene_bytes != c->user_scene_bytes || (fc.scene_grouped && !fc.d_xforms)) {
+        SetError("pm_repaint_groups: the resident scene did not come from the resident paths (pm_upload_scene since, or the last replacement failed)");
+        return PM_ERR_INVALID;
+    }
+    PM_TRY(hipSetDevice(c->device));
+    const WallTimer timer;
+    if (c->scene_bytes > c->dev_scene_alt_cap || !c->d_scene_alt) {
+        // (the other buffer is the one of two replacements back and may be the smaller one; nothing reads it: every replacement ends
+        //  with all frames and hit tests waited for.  Grown once, then never again for scenes of this size.)
+        if (c->d_scene_alt) (void)hipFree(c->d_scene_alt);
+        c->d_scene_alt = nullptr;
+        c->dev_scene_alt_cap = 0;
+        PM_TRY(hipMalloc(&c->d_scene_alt, c->dev_scene_cap));
+        c->dev_scene_alt_cap = c->dev_scene_cap;
+    }
+    hipError_t he = hipSuccess;
+    const int r = pm::FlattenRepaint(c->stream, &c->flatten_cache, paints, n_groups, c->d_scene, c->d_scene_alt, c->scene_bytes, c->n_items, &he);
+    // The two waits of every replacement: the frames and hit tests in flight read the current buffer, and after this call nothing
+    // reads the other one -- which the replacement after this one overwrites.
+    const int rs = SyncAll(c);
+    if (rs != PM_OK || r != PM_OK) {
+        InvalidateScene(c);  // (a HIP failure: the paths' colours and the scene may no longer belong together)
+        if (rs != PM_OK) return rs;
+        return r == PM_ERR_HIP ? HipFail(he, "pm_repaint_groups") : r;
+    }
+    std::swap(c->d_scene, c->d_scene_alt);
+    std::swap(c->dev_scene_cap, c->dev_scene_alt_cap);
+    c->meta_colours_stale = true;
+    c->last_slot = -1;  // (as after every replacement: no frame of this scene yet, pm_read_pixels has nothing to name)
+    c->t_flatten_ms = timer.ms();
+    c->t_index_ms = 0;
+    return PM_OK;
 }
 
 int pm_download_scene(pm_ctx *c, uint8_t *dst, size_t cap, size_t *bytes) {
@@ -2662,6 +2735,8 @@ int pm_fill_coverage(pm_ctx *c, uint32_t item_ix, float *dst, size_t dst_stride_
     std::memcpy(mini, hdr, 8);
     std::memcpy(mini + 8, meta + 8 + 8ull * item_ix, 8);
     std::memcpy(mini + 16, item, 32);
+    if (c->meta_colours_stale)  // (a repainted scene: the record with its colour of today)
+        PM_TRY(hipMemcpy(mini + 16, c->d_scene + c->dev_items_ix + 32ull * item_ix, 32, hipMemcpyDeviceToHost));
     if (root + sizeof(mini) > c->dev_scene_cap) {
         r = ReserveDevice(c, root + sizeof(mini) + 4096, c->scene_bytes);
         if (r != PM_OK) return r;

@@ -40,6 +40,21 @@ struct FlattenCache {
     size_t cap_groups = 0, cap_xforms = 0;
     bool has_groups = false;   // a map is resident (pm_path_groups since the last upload of paths)
     uint32_t max_group = 0;    // ... and its largest index
+    // per-group paint (decision D17, pm_paint.h): the resident paths' own colours, {fill_rgba, stroke_rgba} per path, written
+    // whenever paths are uploaded (d_paths holds the painted ones after pm_repaint_groups); the paint table and its pinned staging
+    // copy.  All three grow only.
+    uint2 *d_orig = nullptr;
+    pm_group_paint *d_paint = nullptr, *h_paint = nullptr;
+    size_t cap_orig = 0, cap_paint = 0;
+    // the call that made the scene now resident: grouped (its table is still in d_xforms) or uniform with this width_scale --
+    // what the thin-line rule of a repainted stroke item needs
+    bool scene_grouped = false;
+    float scene_width_scale = 1.0f;
+    // pm_path_groups behind a grouped scene: the map that scene was made with is kept aside (the buffers change places, once per
+    // scene), since its strokes' width_scales are xforms[that map[p]] whatever the new map says
+    uint32_t *d_groups_scene = nullptr;
+    size_t cap_groups_scene = 0;
+    bool scene_map_aside = false;
     void Free();
     hipError_t Reserve(size_t n_paths, size_t n_els);  // room for this many paths / elements (pm_create)
 };
@@ -67,6 +82,13 @@ int FlattenSetPathGroups(hipStream_t stream, FlattenCache *cache, const uint32_t
 // The transform table of a grouped re-flatten: through the pinned staging copy (grown only when n_groups grows), one asynchronous
 // copy on `stream` in front of the kernels.
 int FlattenStageGroupTable(hipStream_t stream, FlattenCache *cache, const pm_group_xform *xforms, size_t n_groups, hipError_t *hip_error);
+
+// Decision D17: stages the paint table (pinned copy grown only when n_groups grows, one asynchronous copy), paints the resident
+// paths' colours from their originals, copies the resident scene d_src (scene_bytes, n_items, made by the last
+// FlattenEncodeOnDevice from the resident paths) to d_dst and rewrites the items' colour words there.  All on `stream`, nothing
+// waited for, nothing read back.  The caller has checked the table against the resident map.
+int FlattenRepaint(hipStream_t stream, FlattenCache *cache, const pm_group_paint *paints, size_t n_groups, const uint8_t *d_src, uint8_t *d_dst,
+                   size_t scene_bytes, uint32_t n_items, hipError_t *hip_error);
 
 // First item of every resident path in the scene the kernels last wrote (h_base: cache->n_paths entries; path p's items are
 // [h_base[p], h_base[p + 1]), the last path's end at the scene's item count).  Synchronises `stream`.

@@ -19,6 +19,8 @@
 //             wave per styled stroke: the stroke's outline as a compound Fill item in the poly-line's place
 //   K_dash    (only with a dash table, pm_flatten_and_encode_dashed; pm_dash.h, decision D15) a count and one wave per dashed
 //             stroke: the outlines of its dashes, one after another, as that one item's entries
+//   K_paint   (pm_repaint_groups only; pm_paint.h, decision D17) colours of the resident paths and of the resident scene's items
+//             rewritten per group of paths: nothing is flattened
 // f64 arithmetic is kept (gfx950 has full-rate f64 FMA pipes; 2k cubics is
 // nothing) so that the bytes match the CPU path exactly.  -ffp-contract=off.
 #include <hip/hip_runtime.h>
@@ -653,6 +655,7 @@ __global__ void KItemsGrouped(const pm_path *paths, uint32_t n_paths, const pm_p
 
 #include "pm_stroke_outline.h"
 #include "pm_dash.h"
+#include "pm_paint.h"
 
 __global__ void KHeader(uint8_t *scene, const uint32_t *totals, uint32_t fixed_n_items, uint32_t scene_cap) {
     // Encoder::begin_group, src/lib.rs:132-144
@@ -681,6 +684,10 @@ void FlattenCache::Free() {
     if (d_groups) (void)hipFree(d_groups);
     if (d_xforms) (void)hipFree(d_xforms);
     if (h_xforms) (void)hipHostFree(h_xforms);
+    if (d_orig) (void)hipFree(d_orig);
+    if (d_groups_scene) (void)hipFree(d_groups_scene);
+    if (d_paint) (void)hipFree(d_paint);
+    if (h_paint) (void)hipHostFree(h_paint);
     if (h_meta) (void)hipHostFree(h_meta);
     *this = FlattenCache();
 }
@@ -710,6 +717,7 @@ static size_t OutlineScratchWords(size_t n_els) { return 6 + 2 * n_els + 1; }
 hipError_t FlattenCache::Reserve(size_t n_paths, size_t n_els) {
     const size_t n_u32 = ScratchWords(n_paths, n_els) + OutlineScratchWords(n_els);
     hipError_t e = Grow(&d_paths, &cap_paths, n_paths);
+    if (e == hipSuccess) e = Grow(&d_orig, &cap_orig, n_paths);
     if (e == hipSuccess) e = Grow(&d_els, &cap_els, n_els);
     if (e == hipSuccess) e = Grow(&d_u32, &cap_u32, n_u32);
     if (e == hipSuccess) e = Grow(&d_bbox, &cap_bbox, n_els * 4);
@@ -789,10 +797,14 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         cache->resident = true;  // (pm_reflatten of paths without elements: the empty group again)
         cache->n_paths = n_paths;
         cache->n_els = n_els;
+        cache->scene_grouped = false;  // (no item, no stroke: nothing a repaint would ask the table for)
+        cache->scene_width_scale = width_scale;
+        cache->scene_map_aside = false;
         return PM_OK;
     }
 
     PM_HIP_TRY(Grow(&cache->d_paths, &cache->cap_paths, n_paths));
+    PM_HIP_TRY(Grow(&cache->d_orig, &cache->cap_orig, n_paths));
     PM_HIP_TRY(Grow(&cache->d_els, &cache->cap_els, n_els));
     PM_HIP_TRY(Grow(&cache->d_u32, &cache->cap_u32, n_u32));
     PM_HIP_TRY(Grow(&cache->d_bbox, &cache->cap_bbox, n_els * 4));
@@ -803,6 +815,8 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
     if (!use_resident) {
         PM_HIP_TRY(hipMemcpyAsync(d_paths, h_paths, n_paths * sizeof(pm_path), hipMemcpyHostToDevice, stream));
         PM_HIP_TRY(hipMemcpyAsync(d_els, h_els, n_els * sizeof(pm_path_el), hipMemcpyHostToDevice, stream));
+        // (decision D17: the paths' own colours, kept for pm_repaint_groups; new paths bring their own, a paint in force is forgotten)
+        hipLaunchKernelGGL(KKeepColours, dim3((np + 255u) / 256u), dim3(256), 0, stream, static_cast<const pm_path *>(d_paths), np, cache->d_orig);
         // sub-paths open with a MoveTo: an upper bound of the items the encode can produce (a fill and a
         // stroke per sub-path, plus one compound fill per path)
         size_t moves = 0;
@@ -969,6 +983,9 @@ int FlattenEncodeOnDevice(hipStream_t stream, FlattenCache *cache, bool use_resi
         cache->resident = true;
         cache->n_paths = n_paths;
         cache->n_els = n_els;
+        cache->scene_grouped = grouped;
+        cache->scene_width_scale = width_scale;
+        cache->scene_map_aside = false;  // (made with the map in d_groups)
     }
 fail:
     if (hip_err != hipSuccess) {
@@ -980,6 +997,12 @@ fail:
 
 int FlattenSetPathGroups(hipStream_t stream, FlattenCache *cache, const uint32_t *group_of_path, size_t n_paths, hipError_t *hip_error) {
     if (!cache->resident || n_paths != cache->n_paths || !group_of_path) return PM_ERR_INVALID;
+    if (cache->scene_grouped && cache->has_groups && !cache->scene_map_aside) {
+        // (decision D17: a repaint of the resident, grouped scene still needs the map it was made with)
+        std::swap(cache->d_groups, cache->d_groups_scene);
+        std::swap(cache->cap_groups, cache->cap_groups_scene);
+        cache->scene_map_aside = true;
+    }
     hipError_t e = Grow(&cache->d_groups, &cache->cap_groups, std::max<size_t>(n_paths, 1));
     if (e == hipSuccess && n_paths) e = hipMemcpyAsync(cache->d_groups, group_of_path, n_paths * sizeof(uint32_t), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -1014,6 +1037,48 @@ int FlattenStageGroupTable(hipStream_t stream, FlattenCache *cache, const pm_gro
     }
     if (e != hipSuccess) {
         if (hip_error) *hip_error = e;
+        return PM_ERR_HIP;
+    }
+    return PM_OK;
+}
+
+int FlattenRepaint(hipStream_t stream, FlattenCache *cache, const pm_group_paint *paints, size_t n_groups, const uint8_t *d_src, uint8_t *d_dst,
+                   size_t scene_bytes, uint32_t n_items, hipError_t *hip_error) {
+    hipError_t hip_err = hipSuccess;
+    const uint32_t ne = static_cast<uint32_t>(cache->n_els), np = static_cast<uint32_t>(cache->n_paths);
+    if (n_groups > cache->cap_paint || !cache->d_paint || !cache->h_paint) {
+        // (nothing on the device reads the old table: every repaint ends with its stream waited for)
+        if (cache->d_paint) (void)hipFree(cache->d_paint);
+        if (cache->h_paint) (void)hipHostFree(cache->h_paint);
+        cache->d_paint = cache->h_paint = nullptr;
+        cache->cap_paint = 0;
+        const size_t want = n_groups + (n_groups >> 2) + 16;
+        PM_HIP_TRY(hipMalloc(&cache->d_paint, want * sizeof(pm_group_paint)));
+        PM_HIP_TRY(hipHostMalloc(&cache->h_paint, want * sizeof(pm_group_paint), hipHostMallocDefault));
+        cache->cap_paint = want;
+    }
+    std::memcpy(cache->h_paint, paints, n_groups * sizeof(pm_group_paint));
+    PM_HIP_TRY(hipMemcpyAsync(cache->d_paint, cache->h_paint, n_groups * sizeof(pm_group_paint), hipMemcpyHostToDevice, stream));
+    if (np != 0 && ne != 0) {  // (paths without elements were never uploaded: the empty group has nothing to paint)
+        hipLaunchKernelGGL(KPaintPaths, dim3((np + 255u) / 256u), dim3(256), 0, stream, cache->d_paths, np, static_cast<const uint2 *>(cache->d_orig),
+                           static_cast<const uint32_t *>(cache->d_groups), static_cast<const pm_group_paint *>(cache->d_paint));
+    }
+    // everything but the colour words: one copy; frames in flight keep reading d_src
+    PM_HIP_TRY(hipMemcpyAsync(d_dst, d_src, scene_bytes, hipMemcpyDeviceToDevice, stream));
+    if (np != 0 && ne != 0 && n_items != 0) {
+        // d_u32 as FlattenEncodeOnDevice lays it out: el_npts[ne], el_move[ne], el_ptoff[ne + 1], el_mvoff[ne + 1], path_item_base[np], ...
+        const uint32_t *el_mvoff = cache->d_u32 + ne * 2 + (ne + 1);
+        const uint32_t *path_item_base = el_mvoff + ne + 1;
+        // (read only when the scene came from a grouped call: the map and the table of that call)
+        const GroupTable gt{cache->scene_map_aside ? cache->d_groups_scene : cache->d_groups, cache->d_xforms};
+        hipLaunchKernelGGL(KRepaintItems, dim3((n_items + 255u) / 256u), dim3(256), 0, stream, static_cast<const pm_path *>(cache->d_paths), np,
+                           path_item_base, el_mvoff, n_items, cache->scene_grouped, cache->scene_width_scale, gt, d_src, d_dst,
+                           static_cast<uint32_t>(scene_bytes));
+    }
+    PM_HIP_TRY(hipGetLastError());
+fail:
+    if (hip_err != hipSuccess) {
+        if (hip_error) *hip_error = hip_err;
         return PM_ERR_HIP;
     }
     return PM_OK;

@@ -151,6 +151,28 @@ class Renderer:
         _lib.check(self._lib.pm_reflatten_groups(self._h, table.ctypes.data, len(table), C.byref(nbytes), C.byref(nitems)), "pm_reflatten_groups")
         return nbytes.value, nitems.value
 
+    GROUP_PAINT_DTYPE = np.dtype([("tint_rgba", "<u4"), ("opacity", "<u4")])  # pm_group_paint
+
+    def repaint_groups(self, opacities=None, tints=None) -> None:
+        """Fade and tint the groups of the resident paths (decision D17: colours only -- no flatten, no read-back, the scene index
+        and the binning plan stay): opacities is one value 0..255 per group, multiplying every alpha of the group's paths; tints
+        one 0xRRGGBBAA per group, the colour mixed into R, G, B and, as AA, how much of it.  None means the identity for that field
+        (opacity 255, tint 0).  Every call starts from the paths' own colours: paints do not accumulate.  The paint stays in force
+        for later reflatten / reflatten_groups calls, until the next flatten_and_encode."""
+        if opacities is None and tints is None:
+            raise ValueError("repaint_groups needs opacities, tints or both (one value per group)")
+        o = None if opacities is None else np.asarray(opacities).reshape(-1)
+        t = None if tints is None else np.asarray(tints).reshape(-1)
+        if o is not None and t is not None and len(o) != len(t):
+            raise ValueError("opacities and tints are one value per group each")
+        for v in (o, t):
+            if v is not None and v.size and not (np.issubdtype(v.dtype, np.integer) and v.min() >= 0 and v.max() <= 0xFFFFFFFF):
+                raise ValueError("opacities and tints are unsigned integers")
+        table = np.zeros(len(o if o is not None else t), self.GROUP_PAINT_DTYPE)
+        table["opacity"] = 255 if o is None else o
+        table["tint_rgba"] = 0 if t is None else t
+        _lib.check(self._lib.pm_repaint_groups(self._h, table.ctypes.data, len(table)), "pm_repaint_groups")
+
     def reflatten(self, affine, width_scale: float) -> tuple[int, int]:
         """Re-flatten the resident paths of the last flatten_and_encode under a new affine
         (animation: no upload, no allocation); returns (scene_bytes, n_items)."""
