@@ -170,6 +170,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
             PM_PP(ctr_next)->fifo[k].head = 0;
         }
         for (uint32_t k = tid; k < kFifoShards; k += kBinThreads) PM_PP(ctr_next)->done_part[k].count = 0;
+        for (uint32_t k = tid; k < kClassCursors; k += kBinThreads) PM_PP(ctr_next)->cls[k % kClassShards].count[k / kClassShards] = 0;
     }
     if (blockIdx.x == 0 && tid == 0) {
         // The counters of the NEXT frame (the other parity) are idle now: reset them
@@ -179,8 +180,6 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
             PM_PP(ctr_next)->ptcl[k].top = 0;
             PM_PP(ctr_next)->ptcl[k].bin_dwords = 0;
         }
-#pragma unroll
-        for (uint32_t k = 0; k < kClasses; ++k) PM_PP(ctr_next)->cls[k].count = 0;
         PM_PP(ctr_next)->overflow = 0;
         PM_PP(ctr_next)->done_top.parts = 0;
         PM_PP(ctr_next)->done_top.done = 0;
@@ -245,6 +244,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
     const uint32_t shard = rix % kArenaShards;
     const uint32_t shard_quads = PM_PU(tarena_cap) / kArenaShards;
     const uint32_t shard_base = shard * shard_quads;
+    const uint32_t cls_shard = rix % kClassShards;  // ... and its sub-queue of every class queue
     const uint32_t ty = PM_PU(row0) + row_rel;
     const int sx0 = static_cast<int>(strip * kGroupW);
     const int y0 = static_cast<int>(ty * kTileH);
@@ -310,7 +310,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
     // segments in between, under the atomics' round trip.
     bool tail_done = false;
     struct TailState {
-        uint32_t qres;      // what this lane's atomic returned (lane c < kClasses: class c's queue; lane kClasses: tile arena)
+        uint32_t qres;      // what this lane's atomic returned (lane c < kClasses: this row's sub-queue of class c; lane kClasses: tile arena)
         uint32_t list_off;  // the tile's command list inside the strip row's allocation, in quads
         uint32_t packed;    // is_queued | class << 1 | rank of the tile among the row's tiles of its class << 4
         uint32_t qtotal;    // (uniform) quads of the strip row's lists; 0: nothing to queue
@@ -376,7 +376,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
                 Fifo *const ff = &PM_PP(ctr_cur)->fifo[lane == 0u ? 0u : 1u + (blockIdx.x & (kFifoShards - 1u))];
                 if (lane < 2u && give) ts.qres = atomicAdd(&ff->tail, give);
             } else {
-                if (lane < kClasses && lane_cnt) ts.qres = atomicAdd(&PM_PP(ctr_cur)->cls[lane].count, lane_cnt);
+                if (lane < kClasses && lane_cnt) ts.qres = atomicAdd(&PM_PP(ctr_cur)->cls[cls_shard].count[lane], lane_cnt);
             }
             if (lane == kClasses) ts.qres = AtomicAddOneLane(&PM_PP(ctr_cur)->ptcl[shard].top, ts.qtotal);  // (RowTailFinish looks at it)
         }
@@ -430,7 +430,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
         const uint32_t cls = (ts.packed >> 1) & 7u;
         const uint32_t used = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(ts.qres), kClasses)) + 1u;  // (a part's quad 0 stays unused: 0 = "no piece")
         const uint32_t base = shard_base + used;
-        const uint32_t q_base = static_cast<uint32_t>(__shfl(static_cast<int>(ts.qres), static_cast<int>(cls)));  // my class's queue position
+        const uint32_t q_base = static_cast<uint32_t>(__shfl(static_cast<int>(ts.qres), static_cast<int>(cls)));  // my class's position in the row's sub-queue
         // (L.s_alloc[1]: a record of this strip row found the tile arena full -- its pieces do not exist)
         const bool fits = used + ts.qtotal <= shard_quads && used + ts.qtotal >= used && L.s_alloc[1] == 0u;
         // (on overflow the tiles are still queued but marked "no list": the tile kernels skip
@@ -463,7 +463,7 @@ __device__ __forceinline__ void BinStripRows(const FrameParams &P, BinLds<kW, kP
                     if (ix < cap) StoreWT16(PM_PP(fifo) + static_cast<size_t>(1u + (blockIdx.x & (kFifoShards - 1u))) * cap + ix, entry);
                 }
             } else {
-                put_quad(PM_PP(queue) + (cls * PM_PU(queue_cap) + q_base + (ts.packed >> 4)), entry);
+                put_quad(PM_PP(queue) + ((cls * kClassShards + cls_shard) * PM_PU(queue_sub_cap) + q_base + (ts.packed >> 4)), entry);
             }
         }
     };

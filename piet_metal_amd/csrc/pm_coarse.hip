@@ -15,16 +15,8 @@ __global__ __launch_bounds__(kThreads, PM_COARSE_WPS) void pm_coarse_kernel(Fram
 
     const uint32_t lane = LaneId();
     const uint64_t lanes_below = (1ull << lane) - 1ull;
-    uint32_t cls_end[kClasses];  // running totals of the class queues (longest lists first)
-    {
-        uint32_t run = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kClasses; ++k) {
-            run += P.ctr_cur->cls[k].count;
-            cls_end[k] = run;
-        }
-    }
-    const uint32_t n_total = cls_end[kClasses - 1];
+    const uint32_t q_prefix = ClassQueuePrefix(P.ctr_cur, lane);  // lane p: tiles queued in sub-queues 0 .. p (longest lists first)
+    const uint32_t n_total = WaveLast(q_prefix);
 
     // Static snake hand-out over [longest lists..., shortest...]: pass k gives wave g the slot
     // k*G + g (k even) or k*G + (G-1-g) (k odd).  No atomics: one device-scope counter tops out
@@ -35,11 +27,7 @@ __global__ __launch_bounds__(kThreads, PM_COARSE_WPS) void pm_coarse_kernel(Fram
     for (uint32_t pass = 0; pass * n_waves < n_total; ++pass) {
         const uint32_t slot = pass * n_waves + ((pass & 1u) ? (n_waves - 1u - wave_global) : wave_global);
         if (slot >= n_total) continue;
-        uint32_t qix = slot;  // class 0
-#pragma unroll
-        for (uint32_t k = 1; k < kClasses; ++k)
-            if (slot >= cls_end[k - 1]) qix = k * P.queue_cap + (slot - cls_end[k - 1]);
-        const uint4 qe = Scalar4(P.queue[qix]);
+        const uint4 qe = Scalar4(P.queue[ClassQueueEntry(q_prefix, slot, P.queue_sub_cap)]);
         CoarseTile<kCapture>(P, L, qe, lane, lanes_below);
         WaveSync();  // L reuse by the next tile
     }

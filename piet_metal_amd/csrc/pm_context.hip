@@ -149,6 +149,7 @@ int EnvInt(const char *name, int dflt, int lo, int hi) {
 struct FrameSlot {
     uint8_t *d_fb = nullptr;  // this slot's framebuffer (pm_render); pm_render_to uses the caller's
     size_t fb_cap = 0;        // bytes allocated for it, and entries the queue / per-tile tables were allocated for: a viewport that
+    size_t queue_cap = 0;     // entries of d_queue (all sub-queues together); the per-tile tables start behind them
     size_t tables_cap = 0;    // fits keeps the buffers (grow only: a resize to anything smaller than what came before allocates nothing)
     uint32_t *d_arena = nullptr;
     uint32_t arena_cap = 0;  // dwords allocated for this slot (allocated when the slot is first used)
@@ -358,6 +359,14 @@ struct WallTimer {
 uint32_t BandRows(const pm_ctx *c) { return c->row1 - c->row0; }
 size_t BandTiles(const pm_ctx *c) { return std::max<size_t>(static_cast<size_t>(BandRows(c)) * c->tiles_x, 1); }
 
+// Entries of ONE sub-queue of the class queues (pm_device.h) for a work list of `entries`: every tile of every entry of a shard may
+// land in the same class -- kStripTiles x ceil(entries / kClassShards), and never more than the band has tiles.
+size_t QueueSubCap(size_t tiles, size_t entries) {
+    return std::min<size_t>(std::max<size_t>(tiles, 1), pm::kStripTiles * ((std::max<size_t>(entries, 1) + pm::kClassShards - 1) / pm::kClassShards));
+}
+// ... and of all sub-queues together, for the longest work list a viewport of `strip_rows` strip rows can have (every row cut in two)
+size_t QueueEntries(size_t tiles, size_t strip_rows) { return std::max<size_t>(pm::kClassCursors * QueueSubCap(tiles, 2 * strip_rows), 4); }
+
 // Waits for everything this context submitted.  A caller-owned stream (pm_render_to) is never
 // touched after submission -- the caller may have destroyed it: the slot's event, recorded behind
 // the frame at submit time, is waited on instead.
@@ -381,7 +390,7 @@ void FreeSlotViewport(FrameSlot *s) {
     s->fifo_cap = 0;
     s->d_fb = nullptr;
     s->d_queue = nullptr;
-    s->fb_cap = s->tables_cap = 0;
+    s->fb_cap = s->tables_cap = s->queue_cap = 0;
     s->d_tile_state = s->d_tile_ptcl = s->d_tile_ncmd = nullptr;
     s->state_epoch = 0;
 }
@@ -399,9 +408,10 @@ int AllocSlotViewport(pm_ctx *c, FrameSlot *s) {
     if (s->d_fb && s->vp_epoch == c->vp_epoch) return PM_OK;  // (all five buffers exist, or none: a partial set is released below)
     const size_t tiles = BandTiles(c);
     const size_t tables = std::max<size_t>(tiles, 4);
+    const size_t queue_want = QueueEntries(tiles, static_cast<size_t>(BandRows(c)) * c->strips_x);
     const size_t fb_want = std::max<size_t>(c->fb_bytes, 16);
     hipError_t e = hipSuccess;
-    if (s->d_fb && s->d_queue && s->fb_cap >= fb_want && s->tables_cap >= tables) {
+    if (s->d_fb && s->d_queue && s->fb_cap >= fb_want && s->tables_cap >= tables && s->queue_cap >= queue_want) {
         // the buffers of an earlier (larger or equal) viewport serve this one: nothing is released, nothing allocated -- a one-launch
         // frame's FIFOs excepted, whose capacity is the viewport's (they come back when they are next needed, EnsureFifo)
         if (s->d_fifo) (void)hipFree(s->d_fifo);
@@ -409,18 +419,19 @@ int AllocSlotViewport(pm_ctx *c, FrameSlot *s) {
         s->fifo_cap = 0;
     } else {
         FreeSlotViewport(s);  // (buffers of an earlier viewport: released now, when the slot is used again, not by the resize)
-        // two allocations (each costs 50-300 us): the pixels, and -- behind one another -- the class queues (one per cost class)
-        // and the three per-tile tables
+        // two allocations (each costs 50-300 us): the pixels, and -- behind one another -- the class queues (kClassShards sub-queues
+        // per cost class) and the three per-tile tables
         e = hipMalloc(&s->d_fb, fb_want);
-        if (e == hipSuccess) e = hipMalloc(&s->d_queue, pm::kClasses * tables * sizeof(uint4) + 3 * tables * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc(&s->d_queue, queue_want * sizeof(uint4) + 3 * tables * sizeof(uint32_t));
         if (e == hipSuccess) {
             s->fb_cap = fb_want;
             s->tables_cap = tables;
+            s->queue_cap = queue_want;
         }
     }
     s->vp_epoch = c->vp_epoch;
     if (e == hipSuccess) {
-        s->d_tile_state = reinterpret_cast<uint32_t *>(s->d_queue + pm::kClasses * tables);
+        s->d_tile_state = reinterpret_cast<uint32_t *>(s->d_queue + s->queue_cap);  // (behind the queues as they were allocated)
         s->d_tile_ptcl = s->d_tile_state + tables;
         s->d_tile_ncmd = s->d_tile_ptcl + tables;
     }
@@ -430,7 +441,7 @@ int AllocSlotViewport(pm_ctx *c, FrameSlot *s) {
         if (s->d_queue) (void)hipFree(s->d_queue);
         s->d_fb = nullptr;
         s->d_queue = nullptr;
-        s->fb_cap = s->tables_cap = 0;
+        s->fb_cap = s->tables_cap = s->queue_cap = 0;
         s->d_tile_state = s->d_tile_ptcl = s->d_tile_ncmd = nullptr;
         return HipFail(e, "hipMalloc(frame slot viewport buffers)");
     }
@@ -1038,7 +1049,12 @@ int BuildParams(pm_ctx *c, FrameSlot *s, uint8_t *fb, size_t stride, pm::FramePa
     p->bin_grid = c->bin_grid;
     p->sr_empty_dwords = c->sr_empty_dwords;
     p->queue = s->d_queue;
-    p->queue_cap = static_cast<uint32_t>(BandTiles(c));
+    // (the plan's longer work list: the one with the cuts -- the list without them, which frames behind running frames bin from, has fewer entries)
+    p->queue_sub_cap = static_cast<uint32_t>(QueueSubCap(BandTiles(c), std::max(c->n_sr_active, c->n_sr_whole)));
+    if (static_cast<size_t>(pm::kClassCursors) * p->queue_sub_cap > s->queue_cap) {  // (cannot happen: a work list has two entries per strip row at most)
+        SetError("the work list is longer than the slot's tile queues were sized for");
+        return PM_ERR_CAPACITY;
+    }
     p->tile_state = s->d_tile_state;
     p->tarena = s->d_ptcl;
     p->tarena_cap = s->ptcl_cap;
@@ -1827,7 +1843,7 @@ pm_ctx *pm_create(int device, int *err) {
         if (e == hipSuccess) e = hipMalloc(&c->d_band_bbox, 65536 * sizeof(uint2));
         if (e == hipSuccess) e = hipMalloc(&c->d_band_item, 65536 * sizeof(uint32_t));
         if (e == hipSuccess) c->band_cap = 65536;
-        // ... and every frame slot's viewport buffers for anything up to 8192 x 8192 (BASELINE config 5: 256 MB of pixels, 42 MB of queues
+        // ... and every frame slot's viewport buffers for anything up to 8192 x 8192 (BASELINE config 5: 256 MB of pixels, 70 MB of queues
         // and per-tile tables) and its arenas, sized for config 5 (2.2 GB of worst-case binning regions, 1.7 GB of tile arena): four slots are
         // 16 GB, 6 % of the HBM, and ~0.4 s of pm_create.  A resize within that allocates nothing, whichever slot the next frame lands on
         // (round 6 first reserved slot 0 only: config 5's first frame was 1.2 ms when it landed there and 85-115 ms -- one hipMalloc of
@@ -1847,10 +1863,12 @@ pm_ctx *pm_create(int device, int *err) {
             FrameSlot &fs = c->slot[si];
             if (px != 0) {
                 e = hipMalloc(&fs.d_fb, px * 4);
-                if (e == hipSuccess) e = hipMalloc(&fs.d_queue, pm::kClasses * tables * sizeof(uint4) + 3 * tables * sizeof(uint32_t));
+                const size_t queue_pre = QueueEntries(tables, tables / pm::kStripTiles);  // (viewports of whole strips, 8192 x 8192 among them)
+                if (e == hipSuccess) e = hipMalloc(&fs.d_queue, queue_pre * sizeof(uint4) + 3 * tables * sizeof(uint32_t));
                 if (e == hipSuccess) {
                     fs.fb_cap = px * 4;
                     fs.tables_cap = tables;
+                    fs.queue_cap = queue_pre;
                 }
             }
             if (e == hipSuccess) e = hipMalloc(&fs.d_arena, static_cast<size_t>(arena0) * sizeof(uint32_t));
@@ -2686,8 +2704,12 @@ int pm_get_stats(pm_ctx *c, pm_stats *out) {
     if (c->last_slot >= 0) {
         pm::Counters k;
         PM_TRY(hipMemcpy(&k, c->slot[c->last_slot].params.ctr_cur, sizeof(k), hipMemcpyDeviceToHost));
-        for (uint32_t q = 0; q < pm::kClasses; ++q) out->queued_tiles += k.cls[q].count;
-        for (uint32_t q = 0; q < 3; ++q) out->heavy_tiles += k.cls[q].count;  // (n_heavy_classes)
+        for (uint32_t q = 0; q < pm::kClasses; ++q) {
+            for (uint32_t sh = 0; sh < pm::kClassShards; ++sh) {
+                out->queued_tiles += k.cls[sh].count[q];
+                if (q < 3) out->heavy_tiles += k.cls[sh].count[q];  // (n_heavy_classes)
+            }
+        }
         out->arena_used_dwords = 0;
         for (uint32_t i = 0; i < pm::kArenaShards; ++i) out->arena_used_dwords += k.ptcl[i].bin_dwords;
         out->ptcl_used_cmds = 0;
@@ -3044,8 +3066,10 @@ int pm_debug_time_tiles(pm_ctx *c, uint64_t *out, size_t max_slots, size_t *n_sl
     // as pm_fine_kernel decides
     size_t heavy = 0, total = 0;
     for (uint32_t q = 0; q < pm::kClasses; ++q) {
-        total += k.cls[q].count;
-        if (q < 3) heavy += k.cls[q].count;
+        for (uint32_t sh = 0; sh < pm::kClassShards; ++sh) {
+            total += k.cls[sh].count[q];
+            if (q < 3) heavy += k.cls[sh].count[q];
+        }
     }
     const bool dense = heavy * c->dense_factor >= static_cast<size_t>(s->params.fine_grid) * 4u || c->split_mode == 0;
     const size_t slots = dense ? total : 4 * heavy + (total - heavy);

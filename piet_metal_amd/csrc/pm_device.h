@@ -15,6 +15,12 @@ namespace pm {
 // with fine classes that is a longest-processing-time-first schedule, every wave ends up with
 // one long and one short tile instead of whatever the strip rows' atomics happened to interleave.
 constexpr uint32_t kClasses = 8;
+// Every class queue is kept in kClassShards sub-queues, each with a cursor of its own: work-list entry r queues its tiles in
+// sub-queue r % kClassShards of their class (Counters::cls).  kClasses x kClassShards cursors are one per lane of a wave: the tile
+// kernels load them with one instruction and find a slot's queue entry from their prefix sums (pm_kernels_common.h, ClassQueuePrefix).
+constexpr uint32_t kClassShards = 8;
+constexpr uint32_t kClassCursors = kClasses * kClassShards;
+static_assert(kClassCursors == 64, "a cursor per lane");
 
 // Decks of the drawn part of the tile hand-out (pm_fine_kernel).  A deck is a counter on its own cache line; a wave draws
 // from deck wave % n only, so a deck's cards run out when ITS waves have drawn them: with 128 decks of 40 waves the decks
@@ -48,10 +54,18 @@ struct Counters {
         uint32_t bin_dwords;  // dwords of binning records written by the part's strip rows (statistics)
         uint32_t pad[30];
     } ptcl[kArenaShards];
+    // The class queues' cursors: a strip row's tail adds to one cursor per class it queues tiles in (one atomic instruction, a lane
+    // per class), and writes its queue entries only when the results are back.  A frame's rows end within a few microseconds of
+    // each other and nearly all of their tiles are in the two classes of the shortest lists: with one line per CLASS that was a
+    // thousand returning atomics per line inside 8 us, more than a line serves (the tail wave ended 2.0 us behind wave 0's scatter
+    // on average, 7.5 at worst, where an uncontended tail takes 0.3).  So the cursors are sharded like the arena's: work-list entry
+    // r uses line r % kClassShards, which holds its shard's cursor of every class -- a row's atomics go to ONE line, a line serves
+    // an eighth of the rows (4K Tiger: tail 1.2 us on average, 4 at worst), and the tile kernels read eight lines, not 64 (a line
+    // per cursor had the same tails and cost frames in flight 1.3 %: 64 lines requested by every wave of the tile kernel).
     struct {
-        uint32_t count;  // tiles queued in this class
-        uint32_t pad[31];
-    } cls[kClasses];
+        uint32_t count[kClasses];  // tiles queued in this shard's sub-queue of class k
+        uint32_t pad[32 - kClasses];
+    } cls[kClassShards];
     uint32_t overflow;   // set if the command-list arena ran out
     uint32_t pad4[31];
     struct {
@@ -108,6 +122,9 @@ struct Counters {
 // Tile queues: kClasses class queues of 16-byte entries {tile (column | row of the band << 16), first quad of the command list,
 // first piece, candidates | segments << kPieceHitBits of that piece}; the tile kernels walk them
 // statically, longest first, so the expensive tiles start first and the cheap ones fill the tail.
+// Sub-queue s of class k is queue[(k * kClassShards + s) * queue_sub_cap ...]: the host sizes queue_sub_cap per plan for every
+// tile of every work-list entry of a shard landing in one class.  The tile kernels' slot order is class-major, the shards of a
+// class one after the other: longest lists first as before, and a strip row's tiles of a class stay neighbours.
 //
 // Scene index (built once per scene upload by pm_index_kernel, like the ShortBbox
 // array the encoder builds at encode time): segments are grouped in chunks of kChunkSegs
@@ -155,8 +172,8 @@ struct FrameParams {
     uint32_t bin_grid;        // its grid: what the chip holds at once (five workgroups per CU), or a workgroup per strip row
     uint32_t bin_prio_slots;  // strip rows with at least this many segment slots raise their waves' issue priority
     uint32_t sr_empty_dwords; // size of a region no item's bbox reaches
-    uint4 *queue;             // kClasses class queues of {tile, command-list quad, first piece, its candidates | segments << 9}, queue_cap entries each
-    uint32_t queue_cap;
+    uint4 *queue;             // kClasses x kClassShards sub-queues of {tile, command-list quad, first piece, its candidates | segments << 9}, queue_sub_cap entries each
+    uint32_t queue_sub_cap;   // kStripTiles x ceil(work-list entries / kClassShards): what one shard's entries can queue in one class
     uint32_t *tile_state;     // [tiles of the band] 0 = queued for the tile kernels, else resolved colour
     uint4 *tarena;            // tile arena: pieces + per-tile command lists (24-byte records, TestApp/GenTypes.h:430-495)
     uint32_t tarena_cap;      // in quads (16 B)

@@ -30,15 +30,15 @@ __global__ __launch_bounds__(kThreads, kDense ? 6 : 5) void pm_fine_kernel(Frame
         return;
     }
     const uint32_t lane = LaneId(), wave = WaveId();
-    uint32_t cls_end[kClasses];  // running totals of the class queues (longest lists first)
-    {
-        uint32_t run = 0;
-#pragma unroll
-        for (uint32_t k = 0; k < kClasses; ++k) {
-            run += P.ctr_cur->cls[k].count;
-            cls_end[k] = run;
-        }
-    }
+    // lane p: tiles queued in sub-queues 0 .. p (longest lists first).  Wave 0 loads the cursors and hands the sums to the other three
+    // through LDS nobody uses yet (its own command staging; the second barrier: before it builds a list there) -- every wave
+    // loading them itself cost frames in flight 0.5 % (same-box A/B).
+    uint32_t *const q_share = reinterpret_cast<uint32_t *>(S.w[0].cmds);
+    static_assert(sizeof(S.w[0].cmds) >= kClassCursors * sizeof(uint32_t), "the sums fit wave 0's staging area");
+    if (wave == 0) q_share[lane] = ClassQueuePrefix(P.ctr_cur, lane);
+    LdsBarrier();
+    const uint32_t q_prefix = q_share[lane];
+    LdsBarrier();
     // Which workgroup of the hand-out this block is: blocks are dispatched round robin over the 8
     // XCDs (block b runs on XCD b % 8, tools/probes/atomic_probe.hip), and neighbouring slots are
     // tiles of one strip row that read the same binning record -- so runs of four workgroups (16
@@ -50,8 +50,8 @@ __global__ __launch_bounds__(kThreads, kDense ? 6 : 5) void pm_fine_kernel(Frame
     }
     const uint32_t wave_global = wg * kWaves + wave;
     const uint32_t n_waves = P.fine_grid * kWaves;
-    const uint32_t n_tiles = cls_end[kClasses - 1];
-    const uint32_t n_heavy = P.n_heavy_classes ? cls_end[min(P.n_heavy_classes, kClasses) - 1u] : 0u;
+    const uint32_t n_tiles = WaveLast(q_prefix);
+    const uint32_t n_heavy = P.n_heavy_classes ? ClassQueueTotal(q_prefix, min(P.n_heavy_classes, kClasses)) : 0u;
     // A workgroup per long list is a latency measure: it pays while waves would otherwise idle.  Once the long lists alone, at a
     // workgroup each, would occupy every wave of the grid, splitting a tile only costs work: every tile gets one wave.  (The
     // rule used to be "more long lists than WAVES": held-out workload 2 -- 2 k blobs at 2048^2, 16 k tiles, half of them long --
@@ -68,11 +68,7 @@ __global__ __launch_bounds__(kThreads, kDense ? 6 : 5) void pm_fine_kernel(Frame
     // slot -> queue entry
     auto slot_entry = [&](uint32_t slot) -> uint32_t {
         const uint32_t t = slot < s_h ? (slot >> sh) : n_heavy + (slot - s_h);  // position in [longest ... shortest]
-        uint32_t qix = t;
-#pragma unroll
-        for (uint32_t k = 1; k < kClasses; ++k)
-            if (t >= cls_end[k - 1]) qix = k * P.queue_cap + (t - cls_end[k - 1]);
-        return qix;
+        return ClassQueueEntry(q_prefix, t, P.queue_sub_cap);
     };
     auto pass_slot = [&](uint32_t pass) -> uint32_t {
         return pass * n_waves + ((pass & 1u) ? (n_waves - 1u - wave_global) : wave_global);

@@ -132,6 +132,24 @@ __device__ __forceinline__ uint32_t WaveLast(uint32_t v) {
     return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(v), 63));
 }
 
+// ---- slot -> queue entry (the tile kernels' hand-out over the sharded class queues, pm_device.h) ----
+// Lane p loads cursor p of the frame's kClasses x kClassShards cursors (class-major: p = class * kClassShards + shard) -- one
+// instruction, one round trip -- and a wave scan leaves in lane p the tiles queued in sub-queues 0 .. p: position t of
+// [longest lists ... shortest] belongs to the first sub-queue whose running total exceeds it.
+__device__ __forceinline__ uint32_t ClassQueuePrefix(const Counters *ctr, uint32_t lane) {
+    return WaveInclusiveScan(ctr->cls[lane % kClassShards].count[lane / kClassShards]);
+}
+// tiles queued in classes 0 .. n_classes - 1 (n_classes in 1 .. kClasses), as a scalar
+__device__ __forceinline__ uint32_t ClassQueueTotal(uint32_t prefix, uint32_t n_classes) {
+    return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(prefix), static_cast<int>(n_classes * kClassShards - 1u)));
+}
+// Index in FrameParams::queue of position t (wave-uniform, below the total); `prefix` is this lane's word of ClassQueuePrefix.
+__device__ __forceinline__ uint32_t ClassQueueEntry(uint32_t prefix, uint32_t t, uint32_t queue_sub_cap) {
+    const uint32_t owner = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__builtin_ctzll(__ballot(prefix > t) | (1ull << 63)))));
+    const uint32_t below = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(prefix), static_cast<int>(owner ? owner - 1u : 0u)));
+    return owner * queue_sub_cap + (t - (owner ? below : 0u));
+}
+
 // Compiler-level ordering of LDS traffic inside one wave (the LDS itself executes a
 // wave's instructions in order); no instruction is emitted.
 __device__ __forceinline__ void WaveSync() { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); }
