@@ -508,6 +508,22 @@ int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *
 int pm_hit_test_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t flags,
                        void *dev_top_item, void *dev_n_hit, void *hip_stream);
 
+/* The item map of a pixel rectangle (decision D18): for pixel (x0 + i, y0 + j), 0 <= i < w, 0 <= j < h, what pm_hit_test answers
+ * for the point (x0 + i + 0.5f, y0 + j + 0.5f) -- top_item[j * stride + i] (and n_hit[j * stride + i] if n_hit != NULL), decision
+ * D13, same flags.  stride in 32-bit elements, >= w.  Words outside the w x h rectangle are not written.  w == 0 or h == 0 is
+ * PM_OK and writes nothing.  PM_ERR_INVALID, before anything is enqueued: unknown flag bits, no resident scene, x0 + w > 65536 or
+ * y0 + h > 65536 (the viewport limit; every centre is then exact in f32), stride < w, a NULL top_item when w * h > 0.
+ * Needs a scene, no viewport; independent of pm_resize / pm_set_band / pm_set_target_format; frames in flight are not
+ * disturbed.  One workgroup per 16 x 16 tile shares the item cull and the segment stream (pm_hit_frame_kernel): the tiling
+ * does not show in the result.  Synchronises. */
+int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags,
+                 uint32_t *top_item, uint32_t *n_hit, size_t stride);
+
+/* Same on device memory, asynchronous on hip_stream (NULL: the context's stream), ordered as pm_hit_test_device is: it reads
+ * the scene that is resident when it is called, and a later scene replacement waits for it. */
+int pm_hit_frame_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags,
+                        void *dev_top_item, void *dev_n_hit, size_t stride, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

@@ -84,6 +84,7 @@ def main(argv=None) -> int:
     ap.add_argument("--explode", type=float, default=None, metavar="F", help="--frames N (>= 2): instead of spinning, frame k moves every top-level group of the document (element child of the outermost <svg>) by F * k / (N - 1) * (its centre - the document's centre); the groups are re-flattened on the device, each under its own affine")
     ap.add_argument("--fade", action="store_true", help="--frames N (>= 2): instead of spinning, the top-level groups of the document fade out one after another: frame k shows group g of G with opacity round(255 * clamp(1 - k / (N - 1) * G + g, 0, 1)); only the colours of the resident scene are rewritten on the device.  With --explode: both")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
+    ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     args = ap.parse_args(argv)
     try:
         picks = [tuple(float(v) for v in p.split(",")) for p in args.pick]
@@ -123,6 +124,8 @@ def main(argv=None) -> int:
             for (x, y), t in zip(picks, top):
                 print(f"{x:g},{y:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
         if args.frames <= 1:
+            if args.item_map:
+                save_item_map(r, args)
             write_png(args.output, img)
             print(f"{args.output}: {args.width}x{args.height}, {nitems} items, scene {nbytes} bytes", file=sys.stderr)
             return 0
@@ -147,8 +150,19 @@ def main(argv=None) -> int:
             r.sync()
             t_gpu += time.perf_counter() - t0
             write_png(f"{stem}-{k:03d}.png", r.read_pixels())
+        if args.item_map:
+            save_item_map(r, args)
         print(f"{stem}-###.png: {args.frames} frames {args.width}x{args.height}, re-encode + render {t_gpu / args.frames * 1e3:.2f} ms per frame", file=sys.stderr)
     return 0
+
+
+def save_item_map(r, args) -> None:
+    """--item-map: the resident scene's item map over the viewport, to a .npy file, and one line about it."""
+    top = r.hit_frame(0, 0, args.width, args.height)
+    with open(args.item_map, "wb") as f:  # (numpy.save appends ".npy" to a NAME without it: a file object keeps the name given)
+        np.save(f, top)
+    none = int((top == 0xFFFFFFFF).sum())
+    print(f"{args.item_map}: {len(np.unique(top)) - (1 if none else 0)} items visible, {none} pixels with no item")
 
 
 def group_offsets(paths) -> np.ndarray:

@@ -35,7 +35,8 @@
 #include "../../include/piet_metal_amd.h"
 #include "pm_device.h"
 #include "pm_flatten.h"
-#include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing, the one kernel of this unit
+#include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing
+#include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile (the two kernels of this unit)
 #include "pm_layout.h"
 
 namespace {
@@ -2877,6 +2878,68 @@ int HitEnqueue(pm_ctx *c, const float *d_xy, size_t n, uint32_t flags, uint32_t 
     c->hit_pending = true;
     return PM_OK;
 }
+
+// c->d_hit holds `batch` queries: {xy, top_item, n_hit}, 16 bytes each (pm_hit_frame uses the last two)
+hipError_t HitStaging(pm_ctx *c, size_t batch) {
+    if (batch <= c->hit_cap) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    if (c->d_hit) (void)hipFree(c->d_hit);
+    c->d_hit = nullptr;
+    c->hit_cap = 0;
+    e = hipMalloc(&c->d_hit, batch * 16);
+    if (e != hipSuccess) return e;
+    c->hit_cap = batch;
+    return hipSuccess;
+}
+
+// What both item-map calls refuse, before anything is enqueued
+int HitFrameCheck(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, const void *top_item, size_t stride) {
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (static_cast<uint64_t>(x0) + w > 65536u || static_cast<uint64_t>(y0) + h > 65536u) {
+        SetError("pm_hit_frame: the rectangle ends beyond pixel 65 535");
+        return PM_ERR_INVALID;
+    }
+    if (stride < w) {
+        SetError("pm_hit_frame: stride < w");
+        return PM_ERR_INVALID;
+    }
+    if (w != 0 && h != 0 && !top_item) {
+        SetError("pm_hit_frame: top_item is NULL");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// The launch for a rectangle, on q: HitEnqueue's ordering (ev_scene before, ev_hit behind), pm_hit_frame_kernel in between.
+int HitFrameEnqueue(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, size_t stride,
+                    hipStream_t q) {
+    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));
+    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
+    pm::HitFrameParams p{};
+    p.scene = c->d_scene;
+    p.n_items = c->n_items;
+    p.items_ix = c->dev_items_ix;
+    p.bbox_ix = c->dev_bbox_ix;
+    p.chunk_base = c->d_chunk_base;
+    p.chunk_bbox = c->d_chunk_bbox;
+    p.sup_bbox = c->d_sup_bbox;
+    p.top_item = d_top;
+    p.n_hit = d_cnt;
+    p.stride = stride;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.w = w;
+    p.h = h;
+    p.flags = flags;
+    pm::LaunchHitFrame(p, static_cast<uint32_t>(c->n_cus), q);
+    PM_TRY(hipGetLastError());
+    PM_TRY(hipEventRecord(c->ev_hit, q));
+    c->hit_stream = q;
+    c->hit_pending = true;
+    return PM_OK;
+}
 }  // namespace
 
 int pm_hit_test_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t flags, void *dev_top_item, void *dev_n_hit, void *hip_stream) {
@@ -2894,14 +2957,7 @@ int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *
     int r = HitCheck(c, flags);
     if (r != PM_OK || n == 0) return r;
     const size_t batch = std::min(n, kHitBatch);
-    if (batch > c->hit_cap) {  // {xy, top_item, n_hit}: 16 bytes per query
-        PM_TRY(hipStreamSynchronize(c->stream));
-        if (c->d_hit) (void)hipFree(c->d_hit);
-        c->d_hit = nullptr;
-        c->hit_cap = 0;
-        PM_TRY(hipMalloc(&c->d_hit, batch * 16));
-        c->hit_cap = batch;
-    }
+    PM_TRY(HitStaging(c, batch));
     float *d_xy = reinterpret_cast<float *>(c->d_hit);
     uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_hit + c->hit_cap * 8);
     uint32_t *d_cnt = n_hit ? d_top + c->hit_cap : nullptr;
@@ -2913,6 +2969,38 @@ int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *
         PM_TRY(hipMemcpyAsync(top_item + at, d_top, m * 4, hipMemcpyDeviceToHost, c->stream));
         if (n_hit) PM_TRY(hipMemcpyAsync(n_hit + at, d_cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
         PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+// ---- the item map (pm_hit_frame_kernel, pm_hit_frame.h) -----------------------------------------------------------------
+int pm_hit_frame_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, void *dev_top_item, void *dev_n_hit, size_t stride,
+                        void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitFrameCheck(c, x0, y0, w, h, flags, dev_top_item, stride);
+    if (r != PM_OK || w == 0 || h == 0) return r;
+    return HitFrameEnqueue(c, x0, y0, w, h, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit), stride,
+                           hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, uint32_t *top_item, uint32_t *n_hit, size_t stride) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitFrameCheck(c, x0, y0, w, h, flags, top_item, stride);
+    if (r != PM_OK || w == 0 || h == 0) return r;
+    // batches of whole rows, dense on the device (a multiple of the tile's height, so that a batch's tiles are the rectangle's)
+    const size_t rows = std::min<size_t>(h, std::max<size_t>(kHitBatch / w / 16, 1) * 16);
+    PM_TRY(HitStaging(c, rows * w));
+    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_hit + c->hit_cap * 8);
+    uint32_t *d_cnt = n_hit ? d_top + c->hit_cap : nullptr;
+    for (size_t at = 0; at < h; at += rows) {
+        const size_t m = std::min<size_t>(rows, h - at);
+        r = HitFrameEnqueue(c, x0, y0 + static_cast<uint32_t>(at), w, static_cast<uint32_t>(m), flags, d_top, d_cnt, w, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipStreamSynchronize(c->stream));
+        PM_TRY(hipMemcpy2D(top_item + at * stride, stride * 4, d_top, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
+        if (n_hit) PM_TRY(hipMemcpy2D(n_hit + at * stride, stride * 4, d_cnt, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
     }
     return PM_OK;
 }

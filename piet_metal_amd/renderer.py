@@ -14,6 +14,7 @@ provider (render_to) -- plumbing, not the product.
 from __future__ import annotations
 
 import ctypes as C
+import operator
 
 import numpy as np
 
@@ -312,6 +313,44 @@ class Renderer:
         flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
         _lib.check(self._lib.pm_hit_test_device(self._h, xy.data_ptr(), n, flags, top_item.data_ptr(), n_hit.data_ptr() if n_hit is not None else None, s),
                    "pm_hit_test_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def hit_frame(self, x0: int, y0: int, w: int, h: int, skip_transparent: bool = False, counts: bool = False):
+        """The item map of the pixel rectangle [x0, x0 + w) x [y0, y0 + h): uint32 [h, w], what hit_test answers at every pixel's
+        centre (x + 0.5, y + 0.5) -- and with counts=True also how many items contain it.  One workgroup per 16 x 16 tile
+        instead of a wave per point.  Needs a scene, no viewport; the rectangle must end at or before pixel 65 535."""
+        x0, y0, w, h = (operator.index(v) for v in (x0, y0, w, h))
+        if min(x0, y0, w, h) < 0 or x0 + w > 65536 or y0 + h > 65536:
+            raise ValueError("hit_frame needs a rectangle inside [0, 65536) x [0, 65536)")
+        top = np.empty((h, w), np.uint32)
+        cnt = np.empty((h, w), np.uint32) if counts else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_frame(self._h, x0, y0, w, h, flags, top.ctypes.data, cnt.ctypes.data if counts else None, w), "pm_hit_frame")
+        return (top, cnt) if counts else top
+
+    def hit_frame_tensor(self, top_item, n_hit=None, x0: int = 0, y0: int = 0, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: top_item (and n_hit, of the same shape) int32 or uint32 [h, w] with unit
+        stride along a row and any row stride >= w -- a view into a larger tensor works, and what lies outside it is not written.
+        `stream` as in hit_test_tensor."""
+        for t in (top_item, n_hit):
+            if t is not None and not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 2):
+                raise TypeError("hit_frame_tensor writes 2-D CUDA tensors of 32-bit integers")
+        h, w = top_item.shape
+        x0, y0 = operator.index(x0), operator.index(y0)
+        if min(x0, y0) < 0 or x0 + w > 65536 or y0 + h > 65536:
+            raise ValueError("hit_frame_tensor needs a rectangle inside [0, 65536) x [0, 65536)")
+        stride = top_item.stride(0) if h > 1 else max(w, 1)
+        for t in (top_item, n_hit):
+            if t is None or w == 0 or h == 0:
+                continue
+            if tuple(t.shape) != (h, w) or t.stride(1) != 1 or (h > 1 and (t.stride(0) < w or t.stride(0) != stride)):
+                raise ValueError("hit_frame_tensor: rows of unit stride, a row stride >= w, and the same shape and row stride for both tensors")
+        s = stream.cuda_stream if stream is not None else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_frame_device(self._h, x0, y0, w, h, flags, top_item.data_ptr(), n_hit.data_ptr() if n_hit is not None else None,
+                                                 stride, s), "pm_hit_frame_device")
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
