@@ -524,6 +524,32 @@ int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, ui
 int pm_hit_frame_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags,
                         void *dev_top_item, void *dev_n_hit, size_t stride, void *hip_stream);
 
+/* ==== rectangle queries: pick with a tolerance, marquee selection (decision D19) ====
+ * A closed rectangle R = {x0, y0, x1, y1} in scene coordinates TOUCHES an item if the item's shape -- edges included, strokes with
+ * their width -- has a point in common with R, and ENCLOSES it if all of the shape lies in R.  x0 == x1 and / or y0 == y1 is a
+ * valid rectangle (a segment, a point); one with a non-finite value, or with x1 < x0 or y1 < y0, touches and encloses nothing
+ * (not an error).  Same flags, same argument rules and same independence of the viewport as pm_hit_test.
+ *
+ * pm_hit_rects: for each of n rectangles, top_item[k] = the LAST-painted item rectangle k touches, or PM_HIT_NONE; n_hit (may be
+ * NULL) = how many it touches.  A pick with tolerance t around (x, y) is the rectangle {x - t, y - t, x + t, y + t}.
+ * Synchronises. */
+int pm_hit_rects(pm_ctx *c, const float *rects /* n x {x0, y0, x1, y1} */, size_t n, uint32_t flags,
+                 uint32_t *top_item, uint32_t *n_hit);
+/* Same on device memory, asynchronous on hip_stream (NULL: the context's stream), ordered as pm_hit_test_device is. */
+int pm_hit_rects_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t flags,
+                        void *dev_top_item, void *dev_n_hit, void *hip_stream);
+
+#define PM_SEL_TOUCHES 1u
+#define PM_SEL_ENCLOSES 2u
+/* pm_select_rect: ONE rectangle against every item, occluded ones included: item_flags[i] = PM_SEL_* of item i in flat paint
+ * order.  *n_items (may be NULL, like the two counts) is always set; PM_ERR_CAPACITY if cap < n_items, and then nothing else is
+ * written.  Words beyond n_items are not written.  Synchronises. */
+int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *item_flags, size_t cap,
+                   uint32_t *n_items, uint32_t *n_touched, uint32_t *n_enclosed);
+/* Same into device memory (the rectangle itself is read from the host before the call returns), asynchronous on hip_stream,
+ * ordered as pm_hit_test_device is. */
+int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

@@ -43,6 +43,8 @@ PM_SVG_STROKE_DASHES = 16  # needs PM_SVG_STROKE_STYLES
 PM_FMT_RGBA8, PM_FMT_BGRA8 = 0, 1
 PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1
+PM_SEL_TOUCHES = 1
+PM_SEL_ENCLOSES = 2
 
 
 class PathEl(C.Structure):
@@ -172,6 +174,11 @@ SIGNATURES = {
     "pm_hit_frame": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]),
     "pm_hit_frame_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t,
                                       C.c_void_p]),
+    "pm_hit_rects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_hit_rects_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_select_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                 C.POINTER(C.c_uint32)]),
+    "pm_select_rect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

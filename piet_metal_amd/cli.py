@@ -7,6 +7,8 @@
     python -m piet_metal_amd.cli drawing.svg apart.png --frames 30 --explode 1.5    (the top-level groups move apart)
     python -m piet_metal_amd.cli drawing.svg gone.png --frames 30 --fade            (the top-level groups fade out one after another)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
+    python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-tolerance 3   (... or within 3 pixels of them?)
+    python -m piet_metal_amd.cli tiger out.png --select 700,700,900,900    (marquee: what does this rectangle touch, what does it enclose?)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
 machine without a display: the frame is rendered on the MI355X by the same three kernels as
@@ -84,6 +86,8 @@ def main(argv=None) -> int:
     ap.add_argument("--explode", type=float, default=None, metavar="F", help="--frames N (>= 2): instead of spinning, frame k moves every top-level group of the document (element child of the outermost <svg>) by F * k / (N - 1) * (its centre - the document's centre); the groups are re-flattened on the device, each under its own affine")
     ap.add_argument("--fade", action="store_true", help="--frames N (>= 2): instead of spinning, the top-level groups of the document fade out one after another: frame k shows group g of G with opacity round(255 * clamp(1 - k / (N - 1) * G + g, 0, 1)); only the colours of the resident scene are rewritten on the device.  With --explode: both")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
+    ap.add_argument("--pick-tolerance", type=float, default=None, metavar="T", help="every --pick names the topmost item that comes within the square of half side T (pixels) around its point, instead of the item under the point itself")
+    ap.add_argument("--select", default=None, metavar="X0,Y0,X1,Y1", help="marquee selection: print every item the closed rectangle touches, occluded ones included, and the path it came from; items that lie wholly inside it are marked 'enclosed'")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     args = ap.parse_args(argv)
     try:
@@ -92,6 +96,12 @@ def main(argv=None) -> int:
             raise ValueError
     except ValueError:
         ap.error("--pick takes X,Y")
+    try:
+        select = tuple(float(v) for v in args.select.split(",")) if args.select is not None else None
+        if select is not None and len(select) != 4:
+            raise ValueError
+    except ValueError:
+        ap.error("--select takes X0,Y0,X1,Y1")
     if args.explode is not None and args.frames < 2:
         ap.error("--explode needs --frames N with N >= 2")
     if args.fade and args.frames < 2:
@@ -118,11 +128,24 @@ def main(argv=None) -> int:
         nbytes, nitems = r.flatten_and_encode(paths, base, scale)
         r.render()
         img = r.read_pixels()
-        if picks:  # one line per point: the item in flat paint order and the <path> it came from, or none
+        if picks and args.pick_tolerance is None:  # one line per point: the item in flat paint order and the <path> it came from, or none
             top = r.hit_test(np.array(picks, np.float32))
             of_item = r.item_paths()
             for (x, y), t in zip(picks, top):
                 print(f"{x:g},{y:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
+        elif picks:  # the same with a tolerance: the topmost item the square around the point touches
+            top = r.pick(np.array(picks, np.float32), args.pick_tolerance)
+            of_item = r.item_paths()
+            for (x, y), t in zip(picks, top):
+                print(f"{x:g},{y:g} +-{args.pick_tolerance:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
+        if select is not None:  # one line per item the rectangle touches, in paint order
+            touched, enclosed = r.select_rect(*select)
+            of_item = r.item_paths()
+            name = ",".join(f"{v:g}" for v in select)
+            for i in np.flatnonzero(touched):
+                print(f"{name}: item {int(i)} path {int(of_item[i])}" + (" enclosed" if enclosed[i] else ""))
+            if not touched.any():
+                print(f"{name}: none")
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

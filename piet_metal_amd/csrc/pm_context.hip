@@ -36,7 +36,8 @@
 #include "pm_device.h"
 #include "pm_flatten.h"
 #include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing
-#include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile (the two kernels of this unit)
+#include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile
+#include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_layout.h"
 
 namespace {
@@ -339,6 +340,8 @@ struct pm_ctx {
     bool hit_pending = false;          // a hit test was submitted since everything was last waited for
     uint8_t *d_hit = nullptr;          // pm_hit_test's device staging: one batch of {xy, top_item, n_hit}
     size_t hit_cap = 0;                // queries it holds
+    uint8_t *d_rect = nullptr;         // pm_hit_rects' / pm_select_rect's device staging, a buffer of its own (24 bytes per rectangle query)
+    size_t rect_cap = 0;               // bytes it holds
 
     // wall-clock cost of the last scene replacement, host view (pm_get_scene_timings)
     float t_flatten_ms = 0, t_index_ms = 0, t_arena_ms = 0;
@@ -1971,6 +1974,7 @@ void pm_destroy(pm_ctx *c) {
     if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
     if (c->ev_hit) (void)hipEventDestroy(c->ev_hit);
     if (c->d_hit) (void)hipFree(c->d_hit);
+    if (c->d_rect) (void)hipFree(c->d_rect);
     for (hipStream_t q : c->streams) (void)hipStreamDestroy(q);
     delete c;
 }
@@ -3002,6 +3006,148 @@ int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, ui
         PM_TRY(hipMemcpy2D(top_item + at * stride, stride * 4, d_top, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
         if (n_hit) PM_TRY(hipMemcpy2D(n_hit + at * stride, stride * 4, d_cnt, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
     }
+    return PM_OK;
+}
+
+// ---- rectangle queries (pm_hit_rects_kernel, pm_select_rect_kernel, pm_hit_rect.h; decision D19) ---------------------------
+namespace {
+constexpr size_t kRectBatch = static_cast<size_t>(1) << 20;  // pm_hit_rects: queries staged on the device at a time (24 MiB)
+
+// What the two kernels read of the context: the scene, its index and the flags
+pm::HitRectParams RectParams(pm_ctx *c, uint32_t flags) {
+    pm::HitRectParams p{};
+    p.H.scene = c->d_scene;
+    p.H.n_items = c->n_items;
+    p.H.items_ix = c->dev_items_ix;
+    p.H.bbox_ix = c->dev_bbox_ix;
+    p.H.chunk_base = c->d_chunk_base;
+    p.H.chunk_bbox = c->d_chunk_bbox;
+    p.H.sup_bbox = c->d_sup_bbox;
+    p.H.flags = flags;
+    return p;
+}
+
+// HitEnqueue's ordering for a launch on q: behind ev_scene and, on another stream than the last, behind ev_hit ...
+int RectOrderBefore(pm_ctx *c, hipStream_t q) {
+    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));
+    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
+    return PM_OK;
+}
+// ... and ev_hit behind it: whatever replaces the scene waits for it first (SyncAll)
+int RectOrderBehind(pm_ctx *c, hipStream_t q) {
+    PM_TRY(hipGetLastError());
+    PM_TRY(hipEventRecord(c->ev_hit, q));
+    c->hit_stream = q;
+    c->hit_pending = true;
+    return PM_OK;
+}
+
+int HitRectsEnqueue(pm_ctx *c, const float *d_rects, size_t n, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::HitRectParams p = RectParams(c, flags);
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.rects = d_rects + 4 * at;
+        p.H.top_item = d_top + at;
+        p.H.n_hit = d_cnt ? d_cnt + at : nullptr;
+        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchHitRects(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return RectOrderBehind(c, q);
+}
+
+int SelectRectEnqueue(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *d_flags, hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::HitRectParams p = RectParams(c, flags);
+    std::memcpy(p.rect, rect, sizeof(p.rect));
+    p.item_flags = d_flags;
+    pm::LaunchSelectRect(p, static_cast<uint32_t>(c->n_cus), q);
+    return RectOrderBehind(c, q);
+}
+
+// c->d_rect holds `bytes` bytes
+hipError_t RectStaging(pm_ctx *c, size_t bytes) {
+    if (bytes <= c->rect_cap) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return e;
+    if (c->d_rect) (void)hipFree(c->d_rect);
+    c->d_rect = nullptr;
+    c->rect_cap = 0;
+    e = hipMalloc(&c->d_rect, bytes);
+    if (e != hipSuccess) return e;
+    c->rect_cap = bytes;
+    return hipSuccess;
+}
+}  // namespace
+
+int pm_hit_rects_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t flags, void *dev_top_item, void *dev_n_hit, void *hip_stream) {
+    if (!c || (n != 0 && (!dev_rects || !dev_top_item))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    return HitRectsEnqueue(c, static_cast<const float *>(dev_rects), n, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit),
+                           hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_hit_rects(pm_ctx *c, const float *rects, size_t n, uint32_t flags, uint32_t *top_item, uint32_t *n_hit) {
+    if (!c || (n != 0 && (!rects || !top_item))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    const size_t batch = std::min(n, kRectBatch);
+    PM_TRY(RectStaging(c, batch * 24));   // {rect, top_item, n_hit}
+    float *d_rects = reinterpret_cast<float *>(c->d_rect);
+    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_rect + batch * 16);
+    uint32_t *d_cnt = n_hit ? d_top + batch : nullptr;
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(d_rects, rects + 4 * at, m * 16, hipMemcpyHostToDevice, c->stream));
+        r = HitRectsEnqueue(c, d_rects, m, flags, d_top, d_cnt, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(top_item + at, d_top, m * 4, hipMemcpyDeviceToHost, c->stream));
+        if (n_hit) PM_TRY(hipMemcpyAsync(n_hit + at, d_cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream) {
+    if (!c || !rect) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (cap < c->n_items) return PM_ERR_CAPACITY;
+    if (c->n_items == 0) return PM_OK;
+    if (!dev_item_flags) return PM_ERR_INVALID;
+    return SelectRectEnqueue(c, rect, flags, static_cast<uint32_t *>(dev_item_flags), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *item_flags, size_t cap, uint32_t *n_items, uint32_t *n_touched,
+                   uint32_t *n_enclosed) {
+    if (!c) return PM_ERR_INVALID;
+    if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    if (!rect) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n != 0 && !item_flags) return PM_ERR_INVALID;
+    if (n != 0) {
+        PM_TRY(RectStaging(c, n * 4));
+        r = SelectRectEnqueue(c, rect, flags, reinterpret_cast<uint32_t *>(c->d_rect), c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(item_flags, c->d_rect, n * 4, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    uint32_t touched = 0, enclosed = 0;
+    for (size_t i = 0; i < n; ++i) {
+        touched += (item_flags[i] & PM_SEL_TOUCHES) ? 1u : 0u;
+        enclosed += (item_flags[i] & PM_SEL_ENCLOSES) ? 1u : 0u;
+    }
+    if (n_touched) *n_touched = touched;
+    if (n_enclosed) *n_enclosed = enclosed;
     return PM_OK;
 }
 

@@ -355,6 +355,78 @@ class Renderer:
             _warn_default_stream()
             self.sync()
 
+    # ---- rectangle queries (decision D19) ------------------------------------------------
+    def hit_rects(self, rects, skip_transparent: bool = False, counts: bool = False):
+        """The last-painted item every rectangle touches: `rects` is (n, 4) float32 {x0, y0, x1, y1}, closed, in scene coordinates.
+        An item is touched if its shape -- edges included, strokes with their width -- has a point in common with the rectangle.
+        Returns top_item, uint32 [n] (PM_HIT_NONE where nothing is touched), and with counts=True also how many items each
+        rectangle touches.  A rectangle with a non-finite value or with x1 < x0 or y1 < y0 touches nothing.  Needs a scene, no
+        viewport."""
+        rc = np.ascontiguousarray(rects, dtype=np.float32)
+        if rc.ndim != 2 or rc.shape[1] != 4:
+            raise ValueError("hit_rects needs an (n, 4) array of rectangles")
+        n = rc.shape[0]
+        top = np.empty(n, np.uint32)
+        cnt = np.empty(n, np.uint32) if counts else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_rects(self._h, rc.ctypes.data, n, flags, top.ctypes.data, cnt.ctypes.data if counts else None), "pm_hit_rects")
+        return (top, cnt) if counts else top
+
+    def hit_rects_tensor(self, rects, top_item, n_hit=None, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: rects float32 [n, 4], top_item (and n_hit) int32 or uint32 [n], all
+        contiguous.  `stream` as in hit_test_tensor."""
+        if not (rects.is_cuda and top_item.is_cuda) or str(rects.dtype) != "torch.float32" or rects.dim() != 2 or rects.shape[1] != 4 or not rects.is_contiguous():
+            raise TypeError("hit_rects_tensor needs a contiguous CUDA float32 tensor [n, 4]")
+        n = rects.shape[0]
+        for t in (top_item, n_hit):
+            if t is not None and not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.numel() == n and t.is_contiguous()):
+                raise TypeError("hit_rects_tensor writes contiguous CUDA tensors of n 32-bit integers")
+        s = stream.cuda_stream if stream is not None else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_hit_rects_device(self._h, rects.data_ptr(), n, flags, top_item.data_ptr(), n_hit.data_ptr() if n_hit is not None else None, s),
+                   "pm_hit_rects_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    @staticmethod
+    def _pick_rects(points, tolerance) -> np.ndarray:
+        """(n, 4) float32: the square of half side `tolerance` around every point -- {f32(x) - f32(t), f32(y) - f32(t), f32(x) + f32(t),
+        f32(y) + f32(t)}, each value rounded to f32."""
+        xy = np.ascontiguousarray(points, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("pick needs an (n, 2) array of points")
+        t = np.float32(tolerance)
+        return np.concatenate([xy - t, xy + t], axis=1).astype(np.float32)
+
+    def pick(self, points, tolerance, skip_transparent: bool = False, counts: bool = False):
+        """hit_test with a tolerance: the last-painted item that comes within the square of half side `tolerance` around each
+        point (hit_rects on those squares, each value rounded to f32).  A hairline stroke can be clicked this way."""
+        return self.hit_rects(self._pick_rects(points, tolerance), skip_transparent=skip_transparent, counts=counts)
+
+    def select_rect(self, x0, y0, x1, y1, skip_transparent: bool = False):
+        """Marquee selection: (touched, enclosed), bool arrays over the items in flat paint order -- every item the closed rectangle
+        touches, occluded ones included, and every item that lies wholly inside it."""
+        rect = np.array([x0, y0, x1, y1], np.float32)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        words = np.zeros(self.stats()["n_items"], np.uint32)
+        _lib.check(self._lib.pm_select_rect(self._h, rect.ctypes.data, flags, words.ctypes.data, words.size, None, None, None), "pm_select_rect")
+        return (words & _lib.PM_SEL_TOUCHES) != 0, (words & _lib.PM_SEL_ENCLOSES) != 0
+
+    def select_rect_tensor(self, x0, y0, x1, y1, item_flags, stream=None, skip_transparent: bool = False) -> None:
+        """The same into a torch CUDA tensor, asynchronous: item_flags int32 or uint32, contiguous, of at least n_items words --
+        word i becomes PM_SEL_TOUCHES | PM_SEL_ENCLOSES of item i, words beyond n_items are not written."""
+        t = item_flags
+        if not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 1 and t.is_contiguous()):
+            raise TypeError("select_rect_tensor writes a contiguous 1-D CUDA tensor of 32-bit integers")
+        rect = np.array([x0, y0, x1, y1], np.float32)
+        s = stream.cuda_stream if stream is not None else None
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_select_rect_device(self._h, rect.ctypes.data, flags, t.data_ptr(), t.numel(), s), "pm_select_rect_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
     def item_paths(self) -> np.ndarray:
         """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
         n = C.c_uint32(0)
