@@ -326,7 +326,11 @@ int pm_repaint_groups(pm_ctx *c, const pm_group_paint *paints, size_t n_groups);
 int pm_flatten_and_encode_dashed(pm_ctx *c, const pm_path *paths, size_t n_paths, const pm_path_el *els, size_t n_els,
                                  const pm_path_dash *dashes, size_t n_dashes, const float *dash_values, size_t n_dash_values,
                                  const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items);
-/* Copy the resident scene back (parity checks, init_test_scene). */
+/* Copy the resident scene back (parity checks, init_test_scene): the bytes the caller uploaded or the flatten stage wrote, without
+ * the flat form a nested scene gets appended.  With no scene resident -- nothing uploaded yet, or the last replacement failed after
+ * it started, a pm_reflatten_groups included -- it is PM_OK with *bytes = 0 and nothing written; pm_render, pm_fill_coverage,
+ * pm_item_paths, pm_repaint_groups and every hit-test and rectangle query are PM_ERR_INVALID in that state, pm_get_stats reports n_items = 0, and the resident paths, their group map and
+ * their paint stay: pm_reflatten / pm_reflatten_groups bring a scene back, painted as before. */
 int pm_download_scene(pm_ctx *c, uint8_t *dst, size_t cap, size_t *bytes);
 
 /* -drawInMTKView: (PietRenderer.m:59-103): enqueue one frame (binning + per-pixel
