@@ -554,6 +554,26 @@ int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *ite
  * ordered as pm_hit_test_device is. */
 int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream);
 
+/* ==== polygon queries: lasso selection, a marquee in a rotated view (decision D20) ====
+ * The query polygon K has m vertices xy = m x {x, y} in scene coordinates, 3 <= m <= PM_POLYGON_MAX_VERTICES (else
+ * PM_ERR_INVALID), and closes itself.  K TOUCHES an item if the item's outline reaches K's boundary, a point of the item lies in
+ * K, or -- a Fill -- K's first vertex lies in the Fill; it ENCLOSES the item if the outline does not reach the boundary and every
+ * point of the item lies in K (strict at the boundary: an item that only reaches an edge of K is touched, not enclosed).  The
+ * inside of K is by the non-zero rule, with PM_SEL_EVEN_ODD in flags by the even-odd rule; PM_HIT_SKIP_TRANSPARENT as in
+ * pm_select_rect.  Zero area, repeated vertices and self-intersections are valid; a polygon with a non-finite vertex touches and
+ * encloses nothing (not an error).  Output discipline, argument rules and independence of the viewport are pm_select_rect's.
+ * Synchronises. */
+#define PM_POLYGON_MAX_VERTICES 4096u
+#define PM_SEL_EVEN_ODD 2u   /* a flag of the polygon calls alone: the rectangle calls reject it */
+int pm_select_polygon(pm_ctx *c, const float *xy /* m x {x, y}, host */, size_t m, uint32_t flags,
+                      uint32_t *item_flags, size_t cap, uint32_t *n_items, uint32_t *n_touched, uint32_t *n_enclosed);
+/* Same into device memory, asynchronous on hip_stream, ordered as pm_hit_test_device is.  The vertices are read from the host
+ * before the call returns: every call's kernel sees its own polygon, whatever streams the calls go to.  They wait in one of
+ * four staging slots of the context: a fifth call while four are still in flight blocks the host until the oldest of them has
+ * run (nothing is allocated per call). */
+int pm_select_polygon_device(pm_ctx *c, const float *xy /* host */, size_t m, uint32_t flags,
+                             void *dev_item_flags, size_t cap, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

@@ -45,6 +45,8 @@ PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1
 PM_SEL_TOUCHES = 1
 PM_SEL_ENCLOSES = 2
+PM_SEL_EVEN_ODD = 2  # a flag of the polygon calls
+PM_POLYGON_MAX_VERTICES = 4096
 
 
 class PathEl(C.Structure):
@@ -179,6 +181,9 @@ SIGNATURES = {
     "pm_select_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32)]),
     "pm_select_rect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_select_polygon": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                    C.POINTER(C.c_uint32)]),
+    "pm_select_polygon_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

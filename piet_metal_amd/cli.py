@@ -67,6 +67,16 @@ def read_png_rgba(path: str) -> np.ndarray:
     return raw[:, 1:].reshape(h, w, 4).copy()
 
 
+def print_selection(r, values, touched, enclosed) -> None:
+    """--select / --lasso: one line per touched item, in paint order, headed by the query's values as they were given."""
+    of_item = r.item_paths()
+    name = ",".join(f"{v:g}" for v in values)
+    for i in np.flatnonzero(touched):
+        print(f"{name}: item {int(i)} path {int(of_item[i])}" + (" enclosed" if enclosed[i] else ""))
+    if not touched.any():
+        print(f"{name}: none")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m piet_metal_amd.cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("input", help="an .svg file, or 'tiger' for the embedded Ghostscript Tiger")
@@ -88,6 +98,7 @@ def main(argv=None) -> int:
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
     ap.add_argument("--pick-tolerance", type=float, default=None, metavar="T", help="every --pick names the topmost item that comes within the square of half side T (pixels) around its point, instead of the item under the point itself")
     ap.add_argument("--select", default=None, metavar="X0,Y0,X1,Y1", help="marquee selection: print every item the closed rectangle touches, occluded ones included, and the path it came from; items that lie wholly inside it are marked 'enclosed'")
+    ap.add_argument("--lasso", default=None, metavar="X,Y,X,Y,...", help="lasso selection: the same for the polygon of these vertices (three or more, pixels), which closes itself, under the non-zero rule; an item is 'enclosed' if its outline lies inside and does not reach the polygon's boundary")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     args = ap.parse_args(argv)
     try:
@@ -102,6 +113,12 @@ def main(argv=None) -> int:
             raise ValueError
     except ValueError:
         ap.error("--select takes X0,Y0,X1,Y1")
+    try:
+        lasso = tuple(float(v) for v in args.lasso.split(",")) if args.lasso is not None else None
+        if lasso is not None and (len(lasso) < 6 or len(lasso) % 2):
+            raise ValueError
+    except ValueError:
+        ap.error("--lasso takes X,Y,X,Y,... with at least three pairs")
     if args.explode is not None and args.frames < 2:
         ap.error("--explode needs --frames N with N >= 2")
     if args.fade and args.frames < 2:
@@ -139,13 +156,9 @@ def main(argv=None) -> int:
             for (x, y), t in zip(picks, top):
                 print(f"{x:g},{y:g} +-{args.pick_tolerance:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
         if select is not None:  # one line per item the rectangle touches, in paint order
-            touched, enclosed = r.select_rect(*select)
-            of_item = r.item_paths()
-            name = ",".join(f"{v:g}" for v in select)
-            for i in np.flatnonzero(touched):
-                print(f"{name}: item {int(i)} path {int(of_item[i])}" + (" enclosed" if enclosed[i] else ""))
-            if not touched.any():
-                print(f"{name}: none")
+            print_selection(r, select, *r.select_rect(*select))
+        if lasso is not None:  # the same lines for a polygon
+            print_selection(r, lasso, *r.select_polygon(np.array(lasso, np.float32).reshape(-1, 2)))
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

@@ -38,6 +38,7 @@
 #include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing
 #include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
+#include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
 #include "pm_layout.h"
 
 namespace {
@@ -342,6 +343,14 @@ struct pm_ctx {
     size_t hit_cap = 0;                // queries it holds
     uint8_t *d_rect = nullptr;         // pm_hit_rects' / pm_select_rect's device staging, a buffer of its own (24 bytes per rectangle query)
     size_t rect_cap = 0;               // bytes it holds
+    // pm_select_polygon's vertices: a ring of slots, each a pinned host buffer, its device copy and the event behind the kernel
+    // that last read it.  A call takes the next slot, waits for that event, and copies and launches on its own stream.
+    static constexpr int kPolySlots = 4;
+    float *h_poly[kPolySlots] = {};
+    float *d_poly[kPolySlots] = {};
+    hipEvent_t ev_poly[kPolySlots] = {};
+    bool poly_used[kPolySlots] = {};
+    uint32_t poly_next = 0;
 
     // wall-clock cost of the last scene replacement, host view (pm_get_scene_timings)
     float t_flatten_ms = 0, t_index_ms = 0, t_arena_ms = 0;
@@ -1975,6 +1984,11 @@ void pm_destroy(pm_ctx *c) {
     if (c->ev_hit) (void)hipEventDestroy(c->ev_hit);
     if (c->d_hit) (void)hipFree(c->d_hit);
     if (c->d_rect) (void)hipFree(c->d_rect);
+    for (int k = 0; k < pm_ctx::kPolySlots; ++k) {
+        if (c->ev_poly[k]) (void)hipEventDestroy(c->ev_poly[k]);
+        if (c->d_poly[k]) (void)hipFree(c->d_poly[k]);
+        if (c->h_poly[k]) (void)hipHostFree(c->h_poly[k]);
+    }
     for (hipStream_t q : c->streams) (void)hipStreamDestroy(q);
     delete c;
 }
@@ -3137,6 +3151,123 @@ int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *ite
     if (n != 0) {
         PM_TRY(RectStaging(c, n * 4));
         r = SelectRectEnqueue(c, rect, flags, reinterpret_cast<uint32_t *>(c->d_rect), c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(item_flags, c->d_rect, n * 4, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    uint32_t touched = 0, enclosed = 0;
+    for (size_t i = 0; i < n; ++i) {
+        touched += (item_flags[i] & PM_SEL_TOUCHES) ? 1u : 0u;
+        enclosed += (item_flags[i] & PM_SEL_ENCLOSES) ? 1u : 0u;
+    }
+    if (n_touched) *n_touched = touched;
+    if (n_enclosed) *n_enclosed = enclosed;
+    return PM_OK;
+}
+
+// ---- polygon queries (pm_select_polygon_kernel, pm_hit_poly.h; decision D20) -------------------------------------------------
+namespace {
+constexpr size_t kPolyGroupEdges = 16;   // kPolyGroup (pm_hit_poly.h)
+constexpr size_t kPolyVertBytes = static_cast<size_t>(PM_POLYGON_MAX_VERTICES) * 8;
+constexpr size_t kPolyBytes = kPolyVertBytes + PM_POLYGON_MAX_VERTICES / kPolyGroupEdges * 16;   // the vertices, then a box per group of edges
+
+// The ring's buffers, made once at the first polygon query
+hipError_t PolyRing(pm_ctx *c) {
+    for (int k = 0; k < pm_ctx::kPolySlots; ++k) {
+        hipError_t e;
+        if (!c->h_poly[k] && (e = hipHostMalloc(reinterpret_cast<void **>(&c->h_poly[k]), kPolyBytes)) != hipSuccess) return e;
+        if (!c->d_poly[k] && (e = hipMalloc(reinterpret_cast<void **>(&c->d_poly[k]), kPolyBytes)) != hipSuccess) return e;
+        if (!c->ev_poly[k] && (e = hipEventCreateWithFlags(&c->ev_poly[k], hipEventDisableTiming)) != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// flags of a polygon call: PM_SEL_EVEN_ODD is theirs alone, the rest is HitCheck's
+int PolyCheck(pm_ctx *c, const float *xy, size_t m, uint32_t flags) {
+    if (!xy || m < 3 || m > PM_POLYGON_MAX_VERTICES) {
+        SetError("pm_select_polygon: 3 .. PM_POLYGON_MAX_VERTICES vertices");
+        return PM_ERR_INVALID;
+    }
+    return HitCheck(c, flags & ~static_cast<uint32_t>(PM_SEL_EVEN_ODD));
+}
+
+// The launch for a polygon in host memory, on q.  The vertices have left xy when this returns: they are in the slot's pinned
+// buffer, which nothing writes again before the event behind this call's kernel has passed.
+int SelectPolygonEnqueue(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint32_t *d_flags, hipStream_t q) {
+    PM_TRY(PolyRing(c));
+    const uint32_t slot = c->poly_next;
+    c->poly_next = (slot + 1u) % pm_ctx::kPolySlots;
+    if (c->poly_used[slot]) PM_TRY(hipEventSynchronize(c->ev_poly[slot]));
+    std::memcpy(c->h_poly[slot], xy, m * 8);
+    float *gb = c->h_poly[slot] + kPolyVertBytes / 4;
+    const size_t n_groups = (m + kPolyGroupEdges - 1) / kPolyGroupEdges;
+    for (size_t g = 0; g < n_groups; ++g) {   // the ends of edges g * 16 ..: vertices g * 16 .. one past the group's last, mod m
+        float *b = gb + 4 * g;
+        b[0] = b[2] = xy[2 * (g * kPolyGroupEdges)];
+        b[1] = b[3] = xy[2 * (g * kPolyGroupEdges) + 1];
+        for (size_t j = g * kPolyGroupEdges; j <= std::min((g + 1) * kPolyGroupEdges, m); ++j) {
+            const float x = xy[2 * (j % m)], y = xy[2 * (j % m) + 1];
+            b[0] = std::min(b[0], x);
+            b[1] = std::min(b[1], y);
+            b[2] = std::max(b[2], x);
+            b[3] = std::max(b[3], y);
+        }
+    }
+    pm::HitPolyParams p{};
+    p.H = RectParams(c, flags & static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)).H;
+    p.verts = c->d_poly[slot];
+    p.boxes = c->d_poly[slot] + kPolyVertBytes / 4;
+    p.m = static_cast<uint32_t>(m);
+    p.even_odd = (flags & PM_SEL_EVEN_ODD) ? 1u : 0u;
+    p.valid = 1u;
+    p.box[0] = p.box[2] = xy[0];
+    p.box[1] = p.box[3] = xy[1];
+    for (size_t j = 0; j < m; ++j) {
+        const float x = xy[2 * j], y = xy[2 * j + 1];
+        if (!std::isfinite(x) || !std::isfinite(y)) p.valid = 0u;
+        p.box[0] = std::min(p.box[0], x);
+        p.box[1] = std::min(p.box[1], y);
+        p.box[2] = std::max(p.box[2], x);
+        p.box[3] = std::max(p.box[3], y);
+    }
+    p.item_flags = d_flags;
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    PM_TRY(hipMemcpyAsync(c->d_poly[slot], c->h_poly[slot], m * 8, hipMemcpyHostToDevice, q));
+    PM_TRY(hipMemcpyAsync(c->d_poly[slot] + kPolyVertBytes / 4, gb, n_groups * 16, hipMemcpyHostToDevice, q));
+    pm::LaunchSelectPolygon(p, static_cast<uint32_t>(c->n_cus), q);
+    r = RectOrderBehind(c, q);
+    if (r != PM_OK) return r;
+    PM_TRY(hipEventRecord(c->ev_poly[slot], q));
+    c->poly_used[slot] = true;
+    return PM_OK;
+}
+}  // namespace
+
+int pm_select_polygon_device(pm_ctx *c, const float *xy, size_t m, uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = PolyCheck(c, xy, m, flags);
+    if (r != PM_OK) return r;
+    if (cap < c->n_items) return PM_ERR_CAPACITY;
+    if (c->n_items == 0) return PM_OK;
+    if (!dev_item_flags) return PM_ERR_INVALID;
+    return SelectPolygonEnqueue(c, xy, m, flags, static_cast<uint32_t *>(dev_item_flags), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_select_polygon(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint32_t *item_flags, size_t cap, uint32_t *n_items, uint32_t *n_touched,
+                      uint32_t *n_enclosed) {
+    if (!c) return PM_ERR_INVALID;
+    if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    PM_TRY(hipSetDevice(c->device));
+    int r = PolyCheck(c, xy, m, flags);
+    if (r != PM_OK) return r;
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n != 0 && !item_flags) return PM_ERR_INVALID;
+    if (n != 0) {
+        PM_TRY(RectStaging(c, n * 4));
+        r = SelectPolygonEnqueue(c, xy, m, flags, reinterpret_cast<uint32_t *>(c->d_rect), c->stream);
         if (r != PM_OK) return r;
         PM_TRY(hipMemcpyAsync(item_flags, c->d_rect, n * 4, hipMemcpyDeviceToHost, c->stream));
         PM_TRY(hipStreamSynchronize(c->stream));

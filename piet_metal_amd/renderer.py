@@ -427,6 +427,51 @@ class Renderer:
             _warn_default_stream()
             self.sync()
 
+    @staticmethod
+    def _polygon(vertices, skip_transparent, even_odd):
+        xy = np.ascontiguousarray(vertices, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2 or not 3 <= len(xy) <= _lib.PM_POLYGON_MAX_VERTICES:
+            raise ValueError(f"a query polygon is an (m, 2) array of 3 .. {_lib.PM_POLYGON_MAX_VERTICES} vertices")
+        return xy, (_lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0) | (_lib.PM_SEL_EVEN_ODD if even_odd else 0)
+
+    def select_polygon(self, vertices, skip_transparent: bool = False, even_odd: bool = False):
+        """Lasso selection: (touched, enclosed), bool arrays over the items in flat paint order, for the polygon of the (m, 2)
+        vertices, which closes itself.  Touched: the item's outline reaches the polygon's boundary, a point of it lies inside, or the
+        polygon lies inside a Fill.  Enclosed: the outline does not reach the boundary and every point of it lies inside.  The
+        inside is by the non-zero rule, with even_odd by the even-odd rule."""
+        xy, flags = self._polygon(vertices, skip_transparent, even_odd)
+        words = np.zeros(self.stats()["n_items"], np.uint32)
+        _lib.check(self._lib.pm_select_polygon(self._h, xy.ctypes.data, len(xy), flags, words.ctypes.data, words.size, None, None, None), "pm_select_polygon")
+        return (words & _lib.PM_SEL_TOUCHES) != 0, (words & _lib.PM_SEL_ENCLOSES) != 0
+
+    def select_polygon_tensor(self, vertices, item_flags, stream=None, skip_transparent: bool = False, even_odd: bool = False) -> None:
+        """The same into a torch CUDA tensor, asynchronous, as select_rect_tensor: the vertices (host) are read before the call
+        returns."""
+        t = item_flags
+        if not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 1 and t.is_contiguous()):
+            raise TypeError("select_polygon_tensor writes a contiguous 1-D CUDA tensor of 32-bit integers")
+        xy, flags = self._polygon(vertices, skip_transparent, even_odd)
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_select_polygon_device(self._h, xy.ctypes.data, len(xy), flags, t.data_ptr(), t.numel(), s), "pm_select_polygon_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    @staticmethod
+    def rotated_rect_vertices(cx, cy, w, h, angle) -> np.ndarray:
+        """The corners (-w/2, -h/2), (+w/2, -h/2), (+w/2, +h/2), (-w/2, +h/2) of a w x h rectangle, in this order, turned by `angle`
+        (radians, from +x towards +y) about its centre (cx, cy): computed in binary64, each value rounded to f32 once."""
+        ca, sa = np.cos(np.float64(angle)), np.sin(np.float64(angle))
+        hx, hy = np.float64(w) * 0.5, np.float64(h) * 0.5
+        local = np.array([[-hx, -hy], [hx, -hy], [hx, hy], [-hx, hy]], np.float64)
+        out = np.stack([np.float64(cx) + (local[:, 0] * ca - local[:, 1] * sa), np.float64(cy) + (local[:, 0] * sa + local[:, 1] * ca)], axis=1)
+        return out.astype(np.float32)
+
+    def select_rotated_rect(self, cx, cy, w, h, angle, skip_transparent: bool = False):
+        """A marquee dragged in a rotated view: select_polygon of rotated_rect_vertices(cx, cy, w, h, angle) -- the corners
+        (-w/2, -h/2), (+w/2, -h/2), (+w/2, +h/2), (-w/2, +h/2) turned by `angle` radians about (cx, cy), in this order."""
+        return self.select_polygon(self.rotated_rect_vertices(cx, cy, w, h, angle), skip_transparent=skip_transparent)
+
     def item_paths(self) -> np.ndarray:
         """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
         n = C.c_uint32(0)
