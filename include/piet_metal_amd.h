@@ -574,6 +574,33 @@ int pm_select_polygon(pm_ctx *c, const float *xy /* m x {x, y}, host */, size_t 
 int pm_select_polygon_device(pm_ctx *c, const float *xy /* host */, size_t m, uint32_t flags,
                              void *dev_item_flags, size_t cap, void *hip_stream);
 
+/* ==== snapping: the nearest vertex or edge to a cursor (decision D21) ====
+ * A query is {x, y, r} in scene coordinates; out[k] names the nearest piece of geometry within r of query k's point: the item
+ * (flat paint order), PM_SNAP_KIND_VERTEX with the vertex's index in the item and its coordinates, or PM_SNAP_KIND_EDGE with the
+ * index of the segment (the entry index of its start), the parameter t in [0, 1] along it and the nearest point {x, y}; d2 is
+ * the squared distance in binary64.  Fills, Polylines and Lines offer their finite points and their segments (a Fill's closing
+ * segments included), a Circle or an ellipse its centre (vertex 0); a stroke's width plays no part.  Among equal distances the
+ * topmost item wins, then the smallest index.  With both PM_SNAP_VERTICES and PM_SNAP_EDGES a vertex within r wins over every
+ * edge, a nearer one included.  Nothing within r, a non-finite value or r < 0 (not an error): item = PM_HIT_NONE and every
+ * other byte 0.
+ * skip_items: NULL with n_skip == 0, or one word per item (n_skip >= n_items): a non-zero word takes that item out of the search
+ * -- the words pm_select_rect_device / pm_select_polygon_device wrote can be handed to pm_snap_device as they are.
+ * PM_ERR_INVALID, before anything is enqueued: unknown flag bits, neither PM_SNAP_VERTICES nor PM_SNAP_EDGES, no resident scene,
+ * a skip_items / n_skip that break the rule above, a NULL xyr or out with n != 0.  n == 0 is PM_OK and writes nothing; records
+ * beyond n are not written.  Independent of the viewport as pm_hit_test is; frames in flight are not disturbed.  Synchronises. */
+#define PM_SNAP_VERTICES 2u
+#define PM_SNAP_EDGES 4u           /* at least one of the two, else PM_ERR_INVALID; PM_HIT_SKIP_TRANSPARENT (1) as in pm_hit_test */
+#define PM_SNAP_KIND_VERTEX 1u
+#define PM_SNAP_KIND_EDGE 2u
+typedef struct { uint32_t item, kind, index; float t; float x, y; double d2; } pm_snap_result;   /* 32 bytes */
+
+int pm_snap(pm_ctx *c, const float *xyr /* n x {x, y, r} */, size_t n, uint32_t flags,
+            const uint32_t *skip_items, size_t n_skip, pm_snap_result *out);
+/* Same on device memory (dev_out 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is. */
+int pm_snap_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags,
+                   const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

@@ -47,6 +47,8 @@ PM_SEL_TOUCHES = 1
 PM_SEL_ENCLOSES = 2
 PM_SEL_EVEN_ODD = 2  # a flag of the polygon calls
 PM_POLYGON_MAX_VERTICES = 4096
+PM_SNAP_VERTICES, PM_SNAP_EDGES = 2, 4
+PM_SNAP_KIND_VERTEX, PM_SNAP_KIND_EDGE = 1, 2
 
 
 class PathEl(C.Structure):
@@ -184,6 +186,8 @@ SIGNATURES = {
     "pm_select_polygon": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                     C.POINTER(C.c_uint32)]),
     "pm_select_polygon_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_snap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_snap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

@@ -9,6 +9,7 @@
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-tolerance 3   (... or within 3 pixels of them?)
     python -m piet_metal_amd.cli tiger out.png --select 700,700,900,900    (marquee: what does this rectangle touch, what does it enclose?)
+    python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12   (the nearest vertex, or else the nearest edge, within 12 pixels)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
 machine without a display: the frame is rendered on the MI355X by the same three kernels as
@@ -77,6 +78,19 @@ def print_selection(r, values, touched, enclosed) -> None:
         print(f"{name}: none")
 
 
+def print_snaps(r, points, radius, to) -> None:
+    """--snap: one line per point with the record Renderer.snap returns for it."""
+    rec = r.snap(np.array(points, np.float32), radius, vertices=to != "edges", edges=to != "vertices")
+    of_item = r.item_paths()
+    for (x, y), s in zip(points, rec):
+        head = f"{x:g},{y:g} r {radius:g}: "
+        if s["item"] == 0xFFFFFFFF:
+            print(head + "none")
+            continue
+        what = f"vertex {int(s['index'])}" if s["kind"] == 1 else f"edge {int(s['index'])} t {float(s['t']):.9g}"
+        print(head + f"item {int(s['item'])} path {int(of_item[s['item']])} {what} at {float(s['x']):.9g},{float(s['y']):.9g} d2 {float(s['d2']):.17g}")
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m piet_metal_amd.cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("input", help="an .svg file, or 'tiger' for the embedded Ghostscript Tiger")
@@ -99,6 +113,9 @@ def main(argv=None) -> int:
     ap.add_argument("--pick-tolerance", type=float, default=None, metavar="T", help="every --pick names the topmost item that comes within the square of half side T (pixels) around its point, instead of the item under the point itself")
     ap.add_argument("--select", default=None, metavar="X0,Y0,X1,Y1", help="marquee selection: print every item the closed rectangle touches, occluded ones included, and the path it came from; items that lie wholly inside it are marked 'enclosed'")
     ap.add_argument("--lasso", default=None, metavar="X,Y,X,Y,...", help="lasso selection: the same for the polygon of these vertices (three or more, pixels), which closes itself, under the non-zero rule; an item is 'enclosed' if its outline lies inside and does not reach the polygon's boundary")
+    ap.add_argument("--snap", action="append", default=[], metavar="X,Y", help="snapping: print the nearest vertex or point of an edge within --snap-radius of this point (pixels) -- the item, the path it came from, the vertex's or segment's index in the item, the point and its distance; may be repeated")
+    ap.add_argument("--snap-radius", type=float, default=None, metavar="R", help="how far (pixels) a --snap looks; needed with --snap")
+    ap.add_argument("--snap-to", choices=("vertices", "edges", "both"), default="both", help="what a --snap looks for; with 'both' a vertex within the radius wins over every edge")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     args = ap.parse_args(argv)
     try:
@@ -119,6 +136,14 @@ def main(argv=None) -> int:
             raise ValueError
     except ValueError:
         ap.error("--lasso takes X,Y,X,Y,... with at least three pairs")
+    try:
+        snaps = [tuple(float(v) for v in p.split(",")) for p in args.snap]
+        if any(len(p) != 2 for p in snaps):
+            raise ValueError
+    except ValueError:
+        ap.error("--snap takes X,Y")
+    if snaps and args.snap_radius is None:
+        ap.error("--snap needs --snap-radius R")
     if args.explode is not None and args.frames < 2:
         ap.error("--explode needs --frames N with N >= 2")
     if args.fade and args.frames < 2:
@@ -159,6 +184,8 @@ def main(argv=None) -> int:
             print_selection(r, select, *r.select_rect(*select))
         if lasso is not None:  # the same lines for a polygon
             print_selection(r, lasso, *r.select_polygon(np.array(lasso, np.float32).reshape(-1, 2)))
+        if snaps:  # one line per point: the record, and the <path> the item came from
+            print_snaps(r, snaps, args.snap_radius, args.snap_to)
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

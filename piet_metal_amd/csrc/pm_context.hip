@@ -39,6 +39,7 @@
 #include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
+#include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
 #include "pm_layout.h"
 
 namespace {
@@ -3279,6 +3280,87 @@ int pm_select_polygon(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint
     }
     if (n_touched) *n_touched = touched;
     if (n_enclosed) *n_enclosed = enclosed;
+    return PM_OK;
+}
+
+// ---- snapping (pm_snap_kernel, pm_snap.h; decision D21) ------------------------------------------------------------------------
+namespace {
+static_assert(sizeof(pm_snap_result) == 32 && offsetof(pm_snap_result, item) == 0 && offsetof(pm_snap_result, kind) == 4 &&
+                  offsetof(pm_snap_result, index) == 8 && offsetof(pm_snap_result, t) == 12 && offsetof(pm_snap_result, x) == 16 &&
+                  offsetof(pm_snap_result, y) == 20 && offsetof(pm_snap_result, d2) == 24,
+              "the record pm_snap_kernel writes");
+
+// Everything pm_snap / pm_snap_device refuse, before anything is enqueued
+int SnapCheck(pm_ctx *c, const void *xyr, size_t n, uint32_t flags, const void *skip_items, size_t n_skip, const void *out) {
+    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT | PM_SNAP_VERTICES | PM_SNAP_EDGES)) {
+        SetError("pm_snap: unknown flag bits");
+        return PM_ERR_INVALID;
+    }
+    if (!(flags & (PM_SNAP_VERTICES | PM_SNAP_EDGES))) {
+        SetError("pm_snap: PM_SNAP_VERTICES, PM_SNAP_EDGES or both");
+        return PM_ERR_INVALID;
+    }
+    if (!c->d_scene || c->scene_bytes < 8) {
+        SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    if (skip_items ? n_skip < c->n_items : n_skip != 0) {
+        SetError("pm_snap: skip_items holds one word per item, or is NULL with n_skip == 0");
+        return PM_ERR_INVALID;
+    }
+    if (n != 0 && (!xyr || !out)) {
+        SetError("pm_snap: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// HitRectsEnqueue's ordering (ev_scene before, ev_hit behind), pm_snap_kernel in between
+int SnapEnqueue(pm_ctx *c, const float *d_xyr, size_t n, uint32_t flags, const uint32_t *d_skip, uint8_t *d_out, hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::SnapParams p{};
+    p.H = RectParams(c, flags).H;
+    p.skip_items = d_skip;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.xyr = d_xyr + 3 * at;
+        p.out = d_out + 32 * at;
+        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchSnap(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return RectOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_snap_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags, const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = SnapCheck(c, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
+    if (r != PM_OK || n == 0) return r;
+    return SnapEnqueue(c, static_cast<const float *>(dev_xyr), n, flags, static_cast<const uint32_t *>(dev_skip_items), static_cast<uint8_t *>(dev_out),
+                       hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_snap(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_t *skip_items, size_t n_skip, pm_snap_result *out) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = SnapCheck(c, xyr, n, flags, skip_items, n_skip, out);
+    if (r != PM_OK || n == 0) return r;
+    const size_t batch = std::min(n, kRectBatch);
+    const size_t skip_bytes = skip_items ? static_cast<size_t>(c->n_items) * 4 : 0;
+    PM_TRY(RectStaging(c, batch * 44 + skip_bytes));   // {records, queries, skip words}
+    uint8_t *d_out = c->d_rect;
+    float *d_xyr = reinterpret_cast<float *>(c->d_rect + batch * 32);
+    uint32_t *d_skip = skip_items ? reinterpret_cast<uint32_t *>(c->d_rect + batch * 44) : nullptr;
+    if (skip_bytes) PM_TRY(hipMemcpyAsync(d_skip, skip_items, skip_bytes, hipMemcpyHostToDevice, c->stream));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(d_xyr, xyr + 3 * at, m * 12, hipMemcpyHostToDevice, c->stream));
+        r = SnapEnqueue(c, d_xyr, m, flags, d_skip, d_out, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(out + at, d_out, m * 32, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
     return PM_OK;
 }
 

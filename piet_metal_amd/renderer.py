@@ -24,6 +24,10 @@ from .encoder import PathSet
 
 _warned_default_stream = False
 
+# pm_snap_result (decision D21): what Renderer.snap returns, 32 bytes a record
+SNAP_DTYPE = np.dtype([("item", "<u4"), ("kind", "<u4"), ("index", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("d2", "<f8")])
+assert SNAP_DTYPE.itemsize == 32
+
 
 def _warn_default_stream() -> None:
     global _warned_default_stream
@@ -471,6 +475,60 @@ class Renderer:
         """A marquee dragged in a rotated view: select_polygon of rotated_rect_vertices(cx, cy, w, h, angle) -- the corners
         (-w/2, -h/2), (+w/2, -h/2), (+w/2, +h/2), (-w/2, +h/2) turned by `angle` radians about (cx, cy), in this order."""
         return self.select_polygon(self.rotated_rect_vertices(cx, cy, w, h, angle), skip_transparent=skip_transparent)
+
+    # ---- snapping (decision D21) ----------------------------------------------------------
+    @staticmethod
+    def _snap_flags(vertices, edges, skip_transparent) -> int:
+        if not (vertices or edges):
+            raise ValueError("snap needs vertices, edges or both")
+        return (_lib.PM_SNAP_VERTICES if vertices else 0) | (_lib.PM_SNAP_EDGES if edges else 0) | (_lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0)
+
+    def snap(self, points, radius, vertices: bool = True, edges: bool = True, skip_transparent: bool = False, skip_items=None) -> np.ndarray:
+        """The nearest piece of geometry within `radius` of every point: `points` is (n, 2) float32 in scene coordinates, `radius` a
+        scalar or one value per point (each rounded to f32).  Returns a structured array (SNAP_DTYPE) of n records: `item` in flat
+        paint order (PM_HIT_NONE where nothing is within the radius, every other field 0), `kind` 1 for a vertex -- `index` is the
+        point's index in the item, `x, y` the point -- or 2 for an edge -- `index` is the segment's, `t` in [0, 1] the parameter
+        along it, `x, y` the nearest point on it; `d2` is the squared distance.  A Circle or an ellipse offers its centre; a
+        stroke's width plays no part.  Among equal distances the topmost item wins, then the smallest index; with both kinds
+        asked for a vertex within the radius wins over every edge.  skip_items: one word (or bool) per item, non-zero takes the
+        item out of the search."""
+        xy = np.ascontiguousarray(points, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("snap needs an (n, 2) array of points")
+        n = xy.shape[0]
+        rad = np.asarray(radius, dtype=np.float32)
+        if rad.ndim not in (0, 1) or (rad.ndim == 1 and rad.shape[0] != n):
+            raise ValueError("snap needs one radius, or one per point")
+        xyr = np.ascontiguousarray(np.concatenate([xy, np.broadcast_to(rad, (n,))[:, None]], axis=1), dtype=np.float32)
+        flags = self._snap_flags(vertices, edges, skip_transparent)
+        skip = None if skip_items is None else np.ascontiguousarray(np.asarray(skip_items) != 0, dtype=np.uint32)
+        if skip is not None and skip.ndim != 1:
+            raise ValueError("skip_items is one word per item")
+        out = np.zeros(n, SNAP_DTYPE)
+        _lib.check(self._lib.pm_snap(self._h, xyr.ctypes.data, n, flags, skip.ctypes.data if skip is not None else None, skip.size if skip is not None else 0,
+                                     out.ctypes.data), "pm_snap")
+        return out
+
+    def snap_tensor(self, xyr, out, skip_items=None, stream=None, vertices: bool = True, edges: bool = True, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: xyr float32 [n, 3] {x, y, r}, out int32 [n, 8] (the 32-byte records:
+        out.cpu().numpy().view(SNAP_DTYPE)), skip_items None or a tensor of at least n_items 32-bit integers -- what
+        select_rect_tensor / select_polygon_tensor wrote can be handed in as it is --, all contiguous.  `stream` as in
+        hit_test_tensor."""
+        if not (xyr.is_cuda and out.is_cuda) or str(xyr.dtype) != "torch.float32" or xyr.dim() != 2 or xyr.shape[1] != 3 or not xyr.is_contiguous():
+            raise TypeError("snap_tensor needs a contiguous CUDA float32 tensor [n, 3]")
+        n = xyr.shape[0]
+        if str(out.dtype) != "torch.int32" or tuple(out.shape) != (n, 8) or not out.is_contiguous():
+            raise TypeError("snap_tensor writes a contiguous CUDA int32 tensor [n, 8]")
+        t = skip_items
+        if t is not None and not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 1 and t.is_contiguous()):
+            raise TypeError("snap_tensor reads skip_items from a contiguous 1-D CUDA tensor of 32-bit integers")
+        flags = self._snap_flags(vertices, edges, skip_transparent)
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_snap_device(self._h, xyr.data_ptr(), n, flags, t.data_ptr() if t is not None else None, t.numel() if t is not None else 0,
+                                            out.data_ptr(), s), "pm_snap_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
 
     def item_paths(self) -> np.ndarray:
         """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
