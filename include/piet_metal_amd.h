@@ -601,6 +601,43 @@ int pm_snap(pm_ctx *c, const float *xyr /* n x {x, y, r} */, size_t n, uint32_t 
 int pm_snap_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags,
                    const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream);
 
+/* ==== bounds: item, selection and group boxes (decision D22) ====
+ * The bounds of an item are four binary64 values {x0, y0, x1, y1}: the minimum and maximum of its points (a Fill's non-separator
+ * points; a Line's or Polyline's points -+ half its width, the width taken literally; a Circle's centre -+ its radius, an ellipse's
+ * -+ rx, ry), a NaN coordinate ignored, an infinity a value like any other.  An item without points, a stroke of NaN width, an
+ * ellipse with rx <= 0 or ry <= 0 and an item PM_HIT_SKIP_TRANSPARENT skips have the EMPTY box {+inf, +inf, -inf, -inf}, the
+ * identity of the union.  A bound that is a zero is always +0.  A box is BOXED iff x0 <= x1 and y0 <= y1.  For an item of finite
+ * points and a finite width >= 0, pm_select_rect reports PM_SEL_ENCLOSES for a rectangle R iff the item is boxed and its box lies in
+ * R.  Exact within the coordinate bound of DESIGN.md 9 (|v| <= 3.0e38).
+ *
+ * pm_item_bounds: one record per item in flat paint order.  Output discipline is pm_select_rect's: *n_items (may be NULL) is always
+ * set; PM_ERR_CAPACITY if cap < n_items, and then nothing is written; records beyond n_items are not written.  Synchronises. */
+typedef struct { double x0, y0, x1, y1; } pm_bounds;                              /* 32 bytes */
+typedef struct { pm_bounds box; uint32_t n_items, n_boxed; } pm_label_bounds;     /* 40 bytes */
+int pm_item_bounds(pm_ctx *c, uint32_t flags, pm_bounds *out, size_t cap, uint32_t *n_items);
+/* Same into device memory (dev_out 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is. */
+int pm_item_bounds_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap, void *hip_stream);
+
+/* pm_union_bounds: out[l], 0 <= l < n_labels, = the union of the bounds of every item that takes part with label l, how many items
+ * those are (n_items) and how many of them are boxed (n_boxed).  Item i takes part iff the flags do not skip it, item_words is NULL
+ * or item_words[i] & word_mask is non-zero -- the words pm_select_rect_device / pm_select_polygon_device wrote go in as they are,
+ * word_mask PM_SEL_TOUCHES, PM_SEL_ENCLOSES or both --, and its label is below n_labels.  label_of_item NULL: every item has label
+ * 0 (with n_labels == 1: a selection's box and size in one record).  A label nobody carries gets the empty box and two zeros; all
+ * n_labels records are always written.  PM_ERR_INVALID, before anything is enqueued: unknown flag bits (PM_HIT_SKIP_TRANSPARENT is
+ * the only one), no resident scene, n_labels == 0, item_words with n_words < n_items or word_mask == 0, label_of_item with
+ * n_label_words < n_items, a NULL out.  Independent of the viewport; frames in flight are not disturbed.  Synchronises. */
+int pm_union_bounds(pm_ctx *c, uint32_t flags,
+                    const uint32_t *item_words, size_t n_words, uint32_t word_mask,
+                    const uint32_t *label_of_item, size_t n_label_words, uint32_t n_labels,
+                    pm_label_bounds *out);
+/* Same on device memory (dev_out 8-byte aligned, else PM_ERR_INVALID), asynchronous on hip_stream, ordered as pm_hit_rects_device
+ * is.  The records are their own accumulators: nothing is allocated or staged. */
+int pm_union_bounds_device(pm_ctx *c, uint32_t flags,
+                           const void *dev_item_words, size_t n_words, uint32_t word_mask,
+                           const void *dev_label_of_item, size_t n_label_words, uint32_t n_labels,
+                           void *dev_out, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

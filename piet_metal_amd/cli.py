@@ -10,6 +10,8 @@
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-tolerance 3   (... or within 3 pixels of them?)
     python -m piet_metal_amd.cli tiger out.png --select 700,700,900,900    (marquee: what does this rectangle touch, what does it enclose?)
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12   (the nearest vertex, or else the nearest edge, within 12 pixels)
+    python -m piet_metal_amd.cli tiger out.png --bounds --select 700,700,900,900   (where is the picture, where the selection, and how many items)
+    python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
 machine without a display: the frame is rendered on the MI355X by the same three kernels as
@@ -24,6 +26,7 @@ flattened again, pm_repaint_groups rewrites the colour words of the resident sce
 from __future__ import annotations
 
 import argparse
+import json
 import struct
 import sys
 import zlib
@@ -91,6 +94,25 @@ def print_snaps(r, points, radius, to) -> None:
         print(head + f"item {int(s['item'])} path {int(of_item[s['item']])} {what} at {float(s['x']):.9g},{float(s['y']):.9g} d2 {float(s['d2']):.17g}")
 
 
+def bounds_record(r, words=None) -> dict:
+    """--bounds: the box and the counts of the whole scene (words None) or of the items whose word is non-zero."""
+    box, n_items, n_boxed = r.selection_bounds(words)
+    return {"box": [float(v) for v in box], "n_items": n_items, "n_boxed": n_boxed}
+
+
+def fit_affine(base, scale, box, width, height):
+    """--fit: (affine, width_scale) -- `base` followed by the uniform scale and the translation that put `box` into the width x height
+    view, touching its edges along one axis and centred along the other."""
+    x0, y0, x1, y1 = (float(v) for v in box)
+    bw, bh = x1 - x0, y1 - y0
+    s = min(width / bw if bw > 0 else float("inf"), height / bh if bh > 0 else float("inf"))
+    if s == float("inf"):  # a point: nothing to scale
+        s = 1.0
+    tx, ty = (width - s * (x0 + x1)) / 2.0, (height - s * (y0 + y1)) / 2.0
+    a, b, c, d, e, f = base
+    return (s * a, s * b, s * c, s * d, s * e + tx, s * f + ty), scale * s
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m piet_metal_amd.cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("input", help="an .svg file, or 'tiger' for the embedded Ghostscript Tiger")
@@ -116,6 +138,8 @@ def main(argv=None) -> int:
     ap.add_argument("--snap", action="append", default=[], metavar="X,Y", help="snapping: print the nearest vertex or point of an edge within --snap-radius of this point (pixels) -- the item, the path it came from, the vertex's or segment's index in the item, the point and its distance; may be repeated")
     ap.add_argument("--snap-radius", type=float, default=None, metavar="R", help="how far (pixels) a --snap looks; needed with --snap")
     ap.add_argument("--snap-to", choices=("vertices", "edges", "both"), default="both", help="what a --snap looks for; with 'both' a vertex within the radius wins over every edge")
+    ap.add_argument("--bounds", action="store_true", help="bounds: print one JSON line with the box {x0, y0, x1, y1} (pixels) of everything that is drawn and how many items it has -- \"scene\" -- and, with --select / --lasso, the same for the items the query touches -- \"selection\"; with --fit: of the fitted view")
+    ap.add_argument("--fit", action="store_true", help="zoom to fit: before rendering, change the view so that the box of everything drawn -- with --select / --lasso: of what the query touches in the view as given -- fills the output, centred; what --select / --lasso print is what they touched in the view as given")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     args = ap.parse_args(argv)
     try:
@@ -168,6 +192,21 @@ def main(argv=None) -> int:
     with Renderer(args.device) as r:
         r.resize(args.width, args.height)
         nbytes, nitems = r.flatten_and_encode(paths, base, scale)
+        # a selection is taken in the view as given; --fit keeps the items (a re-flatten changes no item's index)
+        selected = r.select_rect(*select) if select is not None else None
+        lassoed = r.select_polygon(np.array(lasso, np.float32).reshape(-1, 2)) if lasso is not None else None
+        chosen = selected[0] if selected is not None else (lassoed[0] if lassoed is not None else None)
+        if args.fit:
+            rec = bounds_record(r, chosen)
+            if not rec["n_boxed"]:
+                ap.error("--fit: nothing to fit the view to")
+            base, scale = fit_affine(base, scale, rec["box"], args.width, args.height)
+            nbytes, nitems = r.reflatten(base, scale)
+        if args.bounds:
+            out = {"scene": bounds_record(r)}
+            if chosen is not None:
+                out["selection"] = bounds_record(r, chosen)
+            print(json.dumps(out))
         r.render()
         img = r.read_pixels()
         if picks and args.pick_tolerance is None:  # one line per point: the item in flat paint order and the <path> it came from, or none
@@ -181,9 +220,9 @@ def main(argv=None) -> int:
             for (x, y), t in zip(picks, top):
                 print(f"{x:g},{y:g} +-{args.pick_tolerance:g}: " + ("none" if t == 0xFFFFFFFF else f"item {int(t)} path {int(of_item[t])}"))
         if select is not None:  # one line per item the rectangle touches, in paint order
-            print_selection(r, select, *r.select_rect(*select))
+            print_selection(r, select, *selected)
         if lasso is not None:  # the same lines for a polygon
-            print_selection(r, lasso, *r.select_polygon(np.array(lasso, np.float32).reshape(-1, 2)))
+            print_selection(r, lasso, *lassoed)
         if snaps:  # one line per point: the record, and the <path> the item came from
             print_snaps(r, snaps, args.snap_radius, args.snap_to)
         if args.frames <= 1:

@@ -40,6 +40,7 @@
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
 #include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
+#include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
 #include "pm_layout.h"
 
 namespace {
@@ -3361,6 +3362,128 @@ int pm_snap(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_
         PM_TRY(hipMemcpyAsync(out + at, d_out, m * 32, hipMemcpyDeviceToHost, c->stream));
         PM_TRY(hipStreamSynchronize(c->stream));
     }
+    return PM_OK;
+}
+
+// ---- bounds (pm_item_bounds_kernel, pm_union_bounds_kernel, pm_bounds.h; decision D22) ---------------------------------------------
+namespace {
+static_assert(sizeof(pm_bounds) == 32 && sizeof(pm_label_bounds) == 40 && offsetof(pm_label_bounds, n_items) == 32 && offsetof(pm_label_bounds, n_boxed) == 36,
+              "the records the bounds kernels write");
+
+// Everything pm_union_bounds / pm_union_bounds_device refuse (HitCheck's part first), before anything is enqueued
+int UnionBoundsCheck(pm_ctx *c, uint32_t flags, const void *item_words, size_t n_words, uint32_t word_mask, const void *label_of_item, size_t n_label_words,
+                     uint32_t n_labels, const void *out) {
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (n_labels == 0) {
+        SetError("pm_union_bounds: n_labels == 0");
+        return PM_ERR_INVALID;
+    }
+    if (item_words && (n_words < c->n_items || word_mask == 0)) {
+        SetError("pm_union_bounds: item_words holds one word per item and word_mask selects a bit of them, or item_words is NULL");
+        return PM_ERR_INVALID;
+    }
+    if (label_of_item && n_label_words < c->n_items) {
+        SetError("pm_union_bounds: label_of_item holds one label per item, or is NULL");
+        return PM_ERR_INVALID;
+    }
+    if (!out || (reinterpret_cast<uintptr_t>(out) & 7u) != 0) {
+        SetError("pm_union_bounds: out is NULL or not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// HitRectsEnqueue's ordering (ev_scene before, ev_hit behind), the launches in between
+int ItemBoundsEnqueue(pm_ctx *c, uint32_t flags, uint8_t *d_out, hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::BoundsParams p{};
+    p.H = RectParams(c, flags).H;
+    p.out = d_out;
+    pm::LaunchItemBounds(p, static_cast<uint32_t>(c->n_cus), q);
+    return RectOrderBehind(c, q);
+}
+
+int UnionBoundsEnqueue(pm_ctx *c, uint32_t flags, const uint32_t *d_words, uint32_t word_mask, const uint32_t *d_labels, uint32_t n_labels, uint8_t *d_out,
+                       hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::BoundsParams p{};
+    p.H = RectParams(c, flags).H;
+    p.item_words = d_words;
+    p.word_mask = word_mask;
+    p.label_of_item = d_labels;
+    p.n_labels = n_labels;
+    p.out = d_out;
+    pm::LaunchUnionBounds(p, static_cast<uint32_t>(c->n_cus), q);
+    return RectOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_item_bounds_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (cap < c->n_items) return PM_ERR_CAPACITY;
+    if (c->n_items == 0) return PM_OK;
+    if (!dev_out || (reinterpret_cast<uintptr_t>(dev_out) & 7u) != 0) {
+        SetError("pm_item_bounds_device: dev_out is NULL or not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return ItemBoundsEnqueue(c, flags, static_cast<uint8_t *>(dev_out), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_item_bounds(pm_ctx *c, uint32_t flags, pm_bounds *out, size_t cap, uint32_t *n_items) {
+    if (!c) return PM_ERR_INVALID;
+    if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n == 0) return PM_OK;
+    if (!out) {
+        SetError("pm_item_bounds: out is NULL");
+        return PM_ERR_INVALID;
+    }
+    PM_TRY(RectStaging(c, n * sizeof(pm_bounds)));
+    r = ItemBoundsEnqueue(c, flags, c->d_rect, c->stream);
+    if (r != PM_OK) return r;
+    PM_TRY(hipMemcpyAsync(out, c->d_rect, n * sizeof(pm_bounds), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
+    return PM_OK;
+}
+
+int pm_union_bounds_device(pm_ctx *c, uint32_t flags, const void *dev_item_words, size_t n_words, uint32_t word_mask, const void *dev_label_of_item,
+                           size_t n_label_words, uint32_t n_labels, void *dev_out, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = UnionBoundsCheck(c, flags, dev_item_words, n_words, word_mask, dev_label_of_item, n_label_words, n_labels, dev_out);
+    if (r != PM_OK) return r;
+    return UnionBoundsEnqueue(c, flags, static_cast<const uint32_t *>(dev_item_words), word_mask, static_cast<const uint32_t *>(dev_label_of_item), n_labels,
+                              static_cast<uint8_t *>(dev_out), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_union_bounds(pm_ctx *c, uint32_t flags, const uint32_t *item_words, size_t n_words, uint32_t word_mask, const uint32_t *label_of_item,
+                    size_t n_label_words, uint32_t n_labels, pm_label_bounds *out) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = UnionBoundsCheck(c, flags, item_words, n_words, word_mask, label_of_item, n_label_words, n_labels, out);
+    if (r != PM_OK) return r;
+    // {records, words, labels}
+    const size_t n = c->n_items, out_bytes = static_cast<size_t>(n_labels) * sizeof(pm_label_bounds);
+    PM_TRY(RectStaging(c, out_bytes + (item_words ? n * 4 : 0) + (label_of_item ? n * 4 : 0)));
+    uint8_t *d_out = c->d_rect;
+    uint32_t *d_words = item_words ? reinterpret_cast<uint32_t *>(c->d_rect + out_bytes) : nullptr;
+    uint32_t *d_labels = label_of_item ? reinterpret_cast<uint32_t *>(c->d_rect + out_bytes + (item_words ? n * 4 : 0)) : nullptr;
+    if (d_words && n) PM_TRY(hipMemcpyAsync(d_words, item_words, n * 4, hipMemcpyHostToDevice, c->stream));
+    if (d_labels && n) PM_TRY(hipMemcpyAsync(d_labels, label_of_item, n * 4, hipMemcpyHostToDevice, c->stream));
+    r = UnionBoundsEnqueue(c, flags, d_words, word_mask, d_labels, n_labels, d_out, c->stream);
+    if (r != PM_OK) return r;
+    PM_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
     return PM_OK;
 }
 

@@ -27,6 +27,9 @@ _warned_default_stream = False
 # pm_snap_result (decision D21): what Renderer.snap returns, 32 bytes a record
 SNAP_DTYPE = np.dtype([("item", "<u4"), ("kind", "<u4"), ("index", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("d2", "<f8")])
 assert SNAP_DTYPE.itemsize == 32
+# pm_label_bounds (decision D22): what Renderer.union_bounds returns, 40 bytes a record
+LABEL_BOUNDS_DTYPE = np.dtype([("box", "<f8", (4,)), ("n_items", "<u4"), ("n_boxed", "<u4")])
+assert LABEL_BOUNDS_DTYPE.itemsize == 40
 
 
 def _warn_default_stream() -> None:
@@ -49,6 +52,7 @@ class Renderer:
         self.device = device
         self.width = self.height = 0
         self.row0 = self.row1 = 0
+        self._path_groups = None  # the map given in set_path_groups (group_bounds labels items with it)
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -122,6 +126,7 @@ class Renderer:
                 ),
                 "pm_flatten_and_encode",
             )
+        self._path_groups = None
         if getattr(paths, "groups", None) is not None:
             self.set_path_groups(paths.groups)
         return nbytes.value, nitems.value
@@ -133,6 +138,7 @@ class Renderer:
         if g.ndim != 1:
             raise ValueError("groups is one uint32 group index per path")
         _lib.check(self._lib.pm_path_groups(self._h, g.ctypes.data, len(g)), "pm_path_groups")
+        self._path_groups = g.copy()
 
     GROUP_XFORM_DTYPE = np.dtype([("m", "<f8", (6,)), ("width_scale", "<f4"), ("reserved", "<u4")])  # pm_group_xform
 
@@ -529,6 +535,92 @@ class Renderer:
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
+
+    # ---- bounds (decision D22) ------------------------------------------------------------
+    @staticmethod
+    def _is_words(t) -> bool:
+        return t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 1 and t.is_contiguous()
+
+    def item_bounds(self, skip_transparent: bool = False) -> np.ndarray:
+        """The bounding box of every item in flat paint order: float64 (n_items, 4), {x0, y0, x1, y1} -- the geometry that is drawn,
+        hit and selected (flattened curves, outlined and dashed strokes, a stroke's half width, a circle's radius), not the path
+        elements.  An item without geometry, and with skip_transparent an item of alpha 0, has the empty box
+        {+inf, +inf, -inf, -inf}."""
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        out = np.empty((self.stats()["n_items"], 4), np.float64)
+        _lib.check(self._lib.pm_item_bounds(self._h, flags, out.ctypes.data, len(out), None), "pm_item_bounds")
+        return out
+
+    def item_bounds_tensor(self, out, stream=None, skip_transparent: bool = False) -> None:
+        """The same into a torch CUDA tensor, asynchronous: out float64 [m, 4] with m >= n_items, contiguous; rows beyond n_items are
+        not written.  `stream` as in hit_test_tensor."""
+        if not (out.is_cuda and str(out.dtype) == "torch.float64" and out.dim() == 2 and out.shape[1] == 4 and out.is_contiguous()):
+            raise TypeError("item_bounds_tensor writes a contiguous CUDA float64 tensor [m, 4]")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_item_bounds_device(self._h, flags, out.data_ptr(), out.shape[0], s), "pm_item_bounds_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def union_bounds(self, labels, n_labels: int, item_flags=None, mask: int = _lib.PM_SEL_TOUCHES | _lib.PM_SEL_ENCLOSES,
+                     skip_transparent: bool = False) -> np.ndarray:
+        """The union of the item boxes per label: a structured array (LABEL_BOUNDS_DTYPE) of n_labels records {box, n_items,
+        n_boxed} -- the union of the boxes of the items that take part with that label, how many they are, and how many of them
+        have a box (x0 <= x1 and y0 <= y1).  labels: one uint32 per item, or None for label 0 everywhere; an item whose label is
+        >= n_labels takes no part.  item_flags: None, or one word per item (what select_rect / select_polygon report as PM_SEL_*
+        words, or any bool array): the item takes part iff word & mask is non-zero.  A label nobody carries has the empty box."""
+        lab = None if labels is None else np.ascontiguousarray(labels, dtype=np.uint32)
+        words = None if item_flags is None else np.ascontiguousarray(item_flags).astype(np.uint32)
+        for v, what in ((lab, "labels"), (words, "item_flags")):
+            if v is not None and v.ndim != 1:
+                raise ValueError(f"{what} is one word per item")
+        if int(n_labels) < 1:
+            raise ValueError("union_bounds needs n_labels >= 1")
+        out = np.zeros(int(n_labels), LABEL_BOUNDS_DTYPE)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_union_bounds(self._h, flags, words.ctypes.data if words is not None else None, words.size if words is not None else 0,
+                                             int(mask) if words is not None else 0, lab.ctypes.data if lab is not None else None,
+                                             lab.size if lab is not None else 0, int(n_labels), out.ctypes.data), "pm_union_bounds")
+        return out
+
+    def union_bounds_tensor(self, out, labels=None, item_flags=None, mask: int = _lib.PM_SEL_TOUCHES | _lib.PM_SEL_ENCLOSES, stream=None,
+                            skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: out int32 [n_labels, 10] (the 40-byte records:
+        out.cpu().numpy().view(LABEL_BOUNDS_DTYPE)), labels and item_flags None or contiguous 1-D tensors of at least n_items 32-bit
+        integers -- what select_rect_tensor / select_polygon_tensor wrote goes in as item_flags as it is.  `stream` as in
+        hit_test_tensor."""
+        if not (out.is_cuda and str(out.dtype) == "torch.int32" and out.dim() == 2 and out.shape[1] == 10 and out.shape[0] >= 1 and out.is_contiguous()):
+            raise TypeError("union_bounds_tensor writes a contiguous CUDA int32 tensor [n_labels, 10]")
+        for t, what in ((labels, "labels"), (item_flags, "item_flags")):
+            if t is not None and not self._is_words(t):
+                raise TypeError(f"union_bounds_tensor reads {what} from a contiguous 1-D CUDA tensor of 32-bit integers")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        w, lab = item_flags, labels
+        _lib.check(self._lib.pm_union_bounds_device(self._h, flags, w.data_ptr() if w is not None else None, w.numel() if w is not None else 0,
+                                                    int(mask) if w is not None else 0, lab.data_ptr() if lab is not None else None,
+                                                    lab.numel() if lab is not None else 0, out.shape[0], out.data_ptr(), s), "pm_union_bounds_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def selection_bounds(self, item_flags=None, mask: int = _lib.PM_SEL_TOUCHES | _lib.PM_SEL_ENCLOSES, skip_transparent: bool = False):
+        """(box, n_items, n_boxed) of a selection: box float64 (4,), the union of the boxes of the items whose word in item_flags has
+        a bit of mask set (None: of every item -- the scene's box, "zoom to fit"), how many items that is, how many have a box."""
+        rec = self.union_bounds(None, 1, item_flags, mask, skip_transparent)[0]
+        return rec["box"].copy(), int(rec["n_items"]), int(rec["n_boxed"])
+
+    def group_bounds(self, item_flags=None, mask: int = _lib.PM_SEL_TOUCHES | _lib.PM_SEL_ENCLOSES, skip_transparent: bool = False) -> np.ndarray:
+        """union_bounds with every item labelled by the group of the path it came from (item_paths composed with the map given in
+        set_path_groups; without a map every path is in group 0): one record per group -- where each group is after
+        reflatten_groups, and, with item_flags, which groups a selection reaches (n_items != 0).  Needs a scene made by
+        flatten_and_encode / reflatten, as item_paths does."""
+        of_item = self.item_paths()
+        groups = self._path_groups
+        if groups is None:
+            return self.union_bounds(None, 1, item_flags, mask, skip_transparent)
+        return self.union_bounds(groups[of_item], int(groups.max()) + 1 if len(groups) else 1, item_flags, mask, skip_transparent)
 
     def item_paths(self) -> np.ndarray:
         """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
