@@ -601,6 +601,34 @@ int pm_snap(pm_ctx *c, const float *xyr /* n x {x, y, r} */, size_t n, uint32_t 
 int pm_snap_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags,
                    const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream);
 
+/* ==== snapping to intersections: the nearest crossing of two edges (decision D23) ====
+ * A query is {x, y, r} as in pm_snap; out[k] names the nearest point within r of query k's point where two edges of the scene
+ * cross.  The edges are pm_snap's: a Fill's segments (closing ones included), a Polyline's, a Line's one; Circles and ellipses
+ * offer none, a stroke's width plays no part, styled and dashed strokes are the outline Fills they are.  An edge is NEAR iff
+ * pm_snap's own distance to it is within r; only pairs of near edges are looked at (a crossing within r lies on two of them).
+ * Two edges that share an end point are no pair -- where they meet is a vertex, which pm_snap offers --, nor are parallel,
+ * collinear or degenerate ones; an end point ON the other edge (a T-junction) counts.  kind = PM_SNAP_KIND_INTERSECTION:
+ * item / index / t name the first edge and the parameter of the crossing along it, item2 / index2 / u the second, {x, y} is the
+ * point, d2 its squared distance in binary64.  The first edge is the one of the topmost item, then of the smaller index; among
+ * equal distances the pair whose first edge is topmost (then of the smallest index) wins, then the same of the second edge.
+ * n_near is the number of near edges.  If it exceeds PM_SNAP_MAX_NEAR_EDGES no pair is looked at: item = PM_HIT_NONE, kind =
+ * PM_SNAP_KIND_TOO_MANY, n_near the full count, every other byte 0 -- ask again with a smaller r.  No crossing within r: item =
+ * PM_HIT_NONE, n_near the count, every other byte 0.  A non-finite value or r < 0 (not an error): item = PM_HIT_NONE and every
+ * other byte 0.
+ * flags: PM_HIT_SKIP_TRANSPARENT or 0, any other bit is PM_ERR_INVALID.  skip_items, the other argument rules, the output
+ * discipline and the ordering are pm_snap's.  Synchronises. */
+#define PM_SNAP_KIND_INTERSECTION 3u
+#define PM_SNAP_KIND_TOO_MANY 4u
+#define PM_SNAP_MAX_NEAR_EDGES 512u
+typedef struct { uint32_t item, kind, index; float t; float x, y; double d2; uint32_t item2, index2; float u; uint32_t n_near; } pm_snap_cross_result;   /* 48 bytes */
+
+int pm_snap_intersections(pm_ctx *c, const float *xyr /* n x {x, y, r} */, size_t n, uint32_t flags,
+                          const uint32_t *skip_items, size_t n_skip, pm_snap_cross_result *out);
+/* Same on device memory (dev_out 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_snap_device is. */
+int pm_snap_intersections_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags,
+                                 const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream);
+
 /* ==== bounds: item, selection and group boxes (decision D22) ====
  * The bounds of an item are four binary64 values {x0, y0, x1, y1}: the minimum and maximum of its points (a Fill's non-separator
  * points; a Line's or Polyline's points -+ half its width, the width taken literally; a Circle's centre -+ its radius, an ellipse's

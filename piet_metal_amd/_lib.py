@@ -49,6 +49,8 @@ PM_SEL_EVEN_ODD = 2  # a flag of the polygon calls
 PM_POLYGON_MAX_VERTICES = 4096
 PM_SNAP_VERTICES, PM_SNAP_EDGES = 2, 4
 PM_SNAP_KIND_VERTEX, PM_SNAP_KIND_EDGE = 1, 2
+PM_SNAP_KIND_INTERSECTION, PM_SNAP_KIND_TOO_MANY = 3, 4
+PM_SNAP_MAX_NEAR_EDGES = 512
 
 
 class PathEl(C.Structure):
@@ -188,6 +190,8 @@ SIGNATURES = {
     "pm_select_polygon_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_snap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_snap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_snap_intersections": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_snap_intersections_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_item_bounds": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_item_bounds_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_union_bounds": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),

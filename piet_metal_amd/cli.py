@@ -10,6 +10,7 @@
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-tolerance 3   (... or within 3 pixels of them?)
     python -m piet_metal_amd.cli tiger out.png --select 700,700,900,900    (marquee: what does this rectangle touch, what does it enclose?)
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12   (the nearest vertex, or else the nearest edge, within 12 pixels)
+    python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12 --snap-to intersections   (the nearest point where two edges cross)
     python -m piet_metal_amd.cli tiger out.png --bounds --select 700,700,900,900   (where is the picture, where the selection, and how many items)
     python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
@@ -83,6 +84,22 @@ def print_selection(r, values, touched, enclosed) -> None:
 
 def print_snaps(r, points, radius, to) -> None:
     """--snap: one line per point with the record Renderer.snap returns for it."""
+    if to == "intersections":
+        from . import _lib
+
+        rec = r.snap_intersections(np.array(points, np.float32), radius)
+        of_item = r.item_paths()
+        for (x, y), s in zip(points, rec):
+            head = f"{x:g},{y:g} r {radius:g}: "
+            if s["kind"] == _lib.PM_SNAP_KIND_TOO_MANY:
+                print(head + f"more than {_lib.PM_SNAP_MAX_NEAR_EDGES} edges within the radius ({int(s['n_near'])}): ask again with a smaller one")
+            elif s["item"] == _lib.PM_HIT_NONE:
+                print(head + "none")
+            else:
+                print(head + f"item {int(s['item'])} path {int(of_item[s['item']])} edge {int(s['index'])} t {float(s['t']):.9g} crosses "
+                      f"item {int(s['item2'])} path {int(of_item[s['item2']])} edge {int(s['index2'])} u {float(s['u']):.9g} "
+                      f"at {float(s['x']):.9g},{float(s['y']):.9g} d2 {float(s['d2']):.17g}")
+        return
     rec = r.snap(np.array(points, np.float32), radius, vertices=to != "edges", edges=to != "vertices")
     of_item = r.item_paths()
     for (x, y), s in zip(points, rec):
@@ -137,7 +154,7 @@ def main(argv=None) -> int:
     ap.add_argument("--lasso", default=None, metavar="X,Y,X,Y,...", help="lasso selection: the same for the polygon of these vertices (three or more, pixels), which closes itself, under the non-zero rule; an item is 'enclosed' if its outline lies inside and does not reach the polygon's boundary")
     ap.add_argument("--snap", action="append", default=[], metavar="X,Y", help="snapping: print the nearest vertex or point of an edge within --snap-radius of this point (pixels) -- the item, the path it came from, the vertex's or segment's index in the item, the point and its distance; may be repeated")
     ap.add_argument("--snap-radius", type=float, default=None, metavar="R", help="how far (pixels) a --snap looks; needed with --snap")
-    ap.add_argument("--snap-to", choices=("vertices", "edges", "both"), default="both", help="what a --snap looks for; with 'both' a vertex within the radius wins over every edge")
+    ap.add_argument("--snap-to", choices=("vertices", "edges", "both", "intersections"), default="both", help="what a --snap looks for; with 'both' a vertex within the radius wins over every edge; 'intersections': the nearest point where two edges cross")
     ap.add_argument("--bounds", action="store_true", help="bounds: print one JSON line with the box {x0, y0, x1, y1} (pixels) of everything that is drawn and how many items it has -- \"scene\" -- and, with --select / --lasso, the same for the items the query touches -- \"selection\"; with --fit: of the fitted view")
     ap.add_argument("--fit", action="store_true", help="zoom to fit: before rendering, change the view so that the box of everything drawn -- with --select / --lasso: of what the query touches in the view as given -- fills the output, centred; what --select / --lasso print is what they touched in the view as given")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")

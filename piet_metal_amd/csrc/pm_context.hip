@@ -40,6 +40,7 @@
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
 #include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
+#include "pm_snap_cross.h" // pm_cross_kernel: snapping to intersections (the nearest crossing of two edges)
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
 #include "pm_layout.h"
 
@@ -3360,6 +3361,87 @@ int pm_snap(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_
         r = SnapEnqueue(c, d_xyr, m, flags, d_skip, d_out, c->stream);
         if (r != PM_OK) return r;
         PM_TRY(hipMemcpyAsync(out + at, d_out, m * 32, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+// ---- snapping to intersections (pm_cross_kernel, pm_snap_cross.h; decision D23) ---------------------------------------------------
+namespace {
+static_assert(sizeof(pm_snap_cross_result) == 48 && offsetof(pm_snap_cross_result, item) == 0 && offsetof(pm_snap_cross_result, kind) == 4 &&
+                  offsetof(pm_snap_cross_result, index) == 8 && offsetof(pm_snap_cross_result, t) == 12 && offsetof(pm_snap_cross_result, x) == 16 &&
+                  offsetof(pm_snap_cross_result, y) == 20 && offsetof(pm_snap_cross_result, d2) == 24 && offsetof(pm_snap_cross_result, item2) == 32 &&
+                  offsetof(pm_snap_cross_result, index2) == 36 && offsetof(pm_snap_cross_result, u) == 40 && offsetof(pm_snap_cross_result, n_near) == 44,
+              "the record pm_cross_kernel writes");
+static_assert(PM_SNAP_MAX_NEAR_EDGES == pm::kCrossMaxNear && PM_SNAP_KIND_INTERSECTION == pm::kSnapKindIntersection && PM_SNAP_KIND_TOO_MANY == pm::kSnapKindTooMany,
+              "pm_snap_cross.h's constants are the header's");
+
+// Everything pm_snap_intersections / pm_snap_intersections_device refuse, before anything is enqueued
+int CrossCheck(pm_ctx *c, const void *xyr, size_t n, uint32_t flags, const void *skip_items, size_t n_skip, const void *out) {
+    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)) {
+        SetError("pm_snap_intersections: unknown flag bits");
+        return PM_ERR_INVALID;
+    }
+    if (!c->d_scene || c->scene_bytes < 8) {
+        SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
+        return PM_ERR_INVALID;
+    }
+    if (skip_items ? n_skip < c->n_items : n_skip != 0) {
+        SetError("pm_snap_intersections: skip_items holds one word per item, or is NULL with n_skip == 0");
+        return PM_ERR_INVALID;
+    }
+    if (n != 0 && (!xyr || !out)) {
+        SetError("pm_snap_intersections: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// SnapEnqueue's ordering (ev_scene before, ev_hit behind), pm_cross_kernel in between
+int CrossEnqueue(pm_ctx *c, const float *d_xyr, size_t n, uint32_t flags, const uint32_t *d_skip, uint8_t *d_out, hipStream_t q) {
+    int r = RectOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::CrossParams p{};
+    p.H = RectParams(c, flags).H;
+    p.skip_items = d_skip;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.xyr = d_xyr + 3 * at;
+        p.out = d_out + 48 * at;
+        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchCross(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return RectOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_snap_intersections_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags, const void *dev_skip_items, size_t n_skip, void *dev_out,
+                                 void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = CrossCheck(c, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
+    if (r != PM_OK || n == 0) return r;
+    return CrossEnqueue(c, static_cast<const float *>(dev_xyr), n, flags, static_cast<const uint32_t *>(dev_skip_items), static_cast<uint8_t *>(dev_out),
+                        hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+}
+
+int pm_snap_intersections(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_t *skip_items, size_t n_skip, pm_snap_cross_result *out) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = CrossCheck(c, xyr, n, flags, skip_items, n_skip, out);
+    if (r != PM_OK || n == 0) return r;
+    const size_t batch = std::min(n, kRectBatch);
+    const size_t skip_bytes = skip_items ? static_cast<size_t>(c->n_items) * 4 : 0;
+    PM_TRY(RectStaging(c, batch * 60 + skip_bytes));   // {records, queries, skip words}
+    uint8_t *d_out = c->d_rect;
+    float *d_xyr = reinterpret_cast<float *>(c->d_rect + batch * 48);
+    uint32_t *d_skip = skip_items ? reinterpret_cast<uint32_t *>(c->d_rect + batch * 60) : nullptr;
+    if (skip_bytes) PM_TRY(hipMemcpyAsync(d_skip, skip_items, skip_bytes, hipMemcpyHostToDevice, c->stream));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(d_xyr, xyr + 3 * at, m * 12, hipMemcpyHostToDevice, c->stream));
+        r = CrossEnqueue(c, d_xyr, m, flags, d_skip, d_out, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(out + at, d_out, m * 48, hipMemcpyDeviceToHost, c->stream));
         PM_TRY(hipStreamSynchronize(c->stream));
     }
     return PM_OK;

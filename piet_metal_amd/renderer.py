@@ -27,6 +27,9 @@ _warned_default_stream = False
 # pm_snap_result (decision D21): what Renderer.snap returns, 32 bytes a record
 SNAP_DTYPE = np.dtype([("item", "<u4"), ("kind", "<u4"), ("index", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("d2", "<f8")])
 assert SNAP_DTYPE.itemsize == 32
+# pm_snap_cross_result (decision D23): what Renderer.snap_intersections returns, 48 bytes a record whose first 32 are SNAP_DTYPE's
+SNAP_CROSS_DTYPE = np.dtype(SNAP_DTYPE.descr + [("item2", "<u4"), ("index2", "<u4"), ("u", "<f4"), ("n_near", "<u4")])
+assert SNAP_CROSS_DTYPE.itemsize == 48
 # pm_label_bounds (decision D22): what Renderer.union_bounds returns, 40 bytes a record
 LABEL_BOUNDS_DTYPE = np.dtype([("box", "<f8", (4,)), ("n_items", "<u4"), ("n_boxed", "<u4")])
 assert LABEL_BOUNDS_DTYPE.itemsize == 40
@@ -532,6 +535,50 @@ class Renderer:
         s = stream.cuda_stream if stream is not None else None
         _lib.check(self._lib.pm_snap_device(self._h, xyr.data_ptr(), n, flags, t.data_ptr() if t is not None else None, t.numel() if t is not None else 0,
                                             out.data_ptr(), s), "pm_snap_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    # ---- snapping to intersections (decision D23) -------------------------------------------
+    def snap_intersections(self, points, radius, skip_transparent: bool = False, skip_items=None) -> np.ndarray:
+        """The nearest crossing of two edges within `radius` of every point; `points`, `radius` and `skip_items` as in snap.
+        Returns a structured array (SNAP_CROSS_DTYPE) of n records: `kind` 3, `item` / `index` / `t` the first edge (the one of the
+        topmost item, then of the smaller index) and the parameter of the crossing along it, `item2` / `index2` / `u` the second,
+        `x, y` the point, `d2` its squared distance, `n_near` the number of edges within the radius.  `item` is PM_HIT_NONE where no
+        two edges cross within the radius, and `kind` 4 where more than PM_SNAP_MAX_NEAR_EDGES (512) edges are within it: ask
+        again with a smaller radius.  Edges that share an end point are no pair (where they meet is a vertex: snap)."""
+        xy = np.ascontiguousarray(points, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("snap_intersections needs an (n, 2) array of points")
+        n = xy.shape[0]
+        rad = np.asarray(radius, dtype=np.float32)
+        if rad.ndim not in (0, 1) or (rad.ndim == 1 and rad.shape[0] != n):
+            raise ValueError("snap_intersections needs one radius, or one per point")
+        xyr = np.ascontiguousarray(np.concatenate([xy, np.broadcast_to(rad, (n,))[:, None]], axis=1), dtype=np.float32)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        skip = None if skip_items is None else np.ascontiguousarray(np.asarray(skip_items) != 0, dtype=np.uint32)
+        if skip is not None and skip.ndim != 1:
+            raise ValueError("skip_items is one word per item")
+        out = np.zeros(n, SNAP_CROSS_DTYPE)
+        _lib.check(self._lib.pm_snap_intersections(self._h, xyr.ctypes.data, n, flags, skip.ctypes.data if skip is not None else None,
+                                                   skip.size if skip is not None else 0, out.ctypes.data), "pm_snap_intersections")
+        return out
+
+    def snap_intersections_tensor(self, xyr, out, skip_items=None, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: xyr float32 [n, 3] {x, y, r}, out int32 [n, 12] (the 48-byte records:
+        out.cpu().numpy().view(SNAP_CROSS_DTYPE)), skip_items and `stream` as in snap_tensor."""
+        if not (xyr.is_cuda and out.is_cuda) or str(xyr.dtype) != "torch.float32" or xyr.dim() != 2 or xyr.shape[1] != 3 or not xyr.is_contiguous():
+            raise TypeError("snap_intersections_tensor needs a contiguous CUDA float32 tensor [n, 3]")
+        n = xyr.shape[0]
+        if str(out.dtype) != "torch.int32" or tuple(out.shape) != (n, 12) or not out.is_contiguous():
+            raise TypeError("snap_intersections_tensor writes a contiguous CUDA int32 tensor [n, 12]")
+        t = skip_items
+        if t is not None and not (t.is_cuda and t.element_size() == 4 and not t.is_floating_point() and t.dim() == 1 and t.is_contiguous()):
+            raise TypeError("snap_intersections_tensor reads skip_items from a contiguous 1-D CUDA tensor of 32-bit integers")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_snap_intersections_device(self._h, xyr.data_ptr(), n, flags, t.data_ptr() if t is not None else None,
+                                                          t.numel() if t is not None else 0, out.data_ptr(), s), "pm_snap_intersections_device")
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
