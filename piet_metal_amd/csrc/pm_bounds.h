@@ -1,7 +1,9 @@
 // pm_item_bounds_kernel, pm_union_bounds_kernel: bounds queries -- the bounding box of every item of the resident scene, and the
 // union of the boxes of the items that carry a label (a group, a selection) with how many there are.  Not on the frame path: like
-// the other query kernels they read the scene and the scene index, nothing a frame writes.  Included by pm_context.hip after
-// pm_snap.h; the constants and the launch shape of pm_select_rect_kernel are used as they are.
+// the other query kernels they read the scene and the scene index, nothing a frame writes.  Included by pm_context.hip; the
+// item head, the constants and the launch shape of pm_select_rect_kernel (a wave per step of 64 items: FirstWaveUnit / GridWaves) are
+// pm_query_common.h's, as they are.  The walks there put lane 0 at the TOPMOST item of a step; here lane l has item 64 step + l, so that
+// a run of equal labels is a run of lanes, and the step keeps its own body.
 //
 // What the bounds of an item are is decision D22: binary64 values of the scene's f32 / u16 values, one rounding per
 // written operation (-ffp-contract=off) -- tests/np_bounds.py states the same in numpy from the points alone and the records must
@@ -31,13 +33,13 @@
 // the record pm_label_bounds is its own accumulator.  No float atomics, no wave waits for another, no LDS, no scratch.
 #pragma once
 
-#include "pm_snap.h"
+#include "pm_query_common.h"
 
 namespace pm {
 
-// One launch of either kernel.  H: the scene, its index and the flags (H.xy, H.top_item, H.n_hit and H.n are unused).
+// One launch of either kernel
 struct BoundsParams {
-    HitParams H;
+    SceneView V;
     const uint32_t *item_words;     // union: [n_items] the item takes part iff word & word_mask (nullptr: every item)
     const uint32_t *label_of_item;  // union: [n_items] (nullptr: every item has label 0)
     uint32_t word_mask, n_labels;
@@ -85,26 +87,27 @@ struct BoundsSource {
     bool chunks = false, compound = false;
 };
 
-__device__ __forceinline__ void BoundsAddEntry(const HitParams &P, const BoundsSource &S, uint32_t e, BoundsAcc &a) {
+__device__ __forceinline__ void BoundsAddEntry(const SceneView &V, const BoundsSource &S, uint32_t e, BoundsAcc &a) {
     if (S.chunks) {
-        BoundsAddChunk(a, P.chunk_bbox[S.first + e]);
+        BoundsAddChunk(a, V.chunk_bbox[S.first + e]);
     } else {
         const float2 p = LoadF2(S.pts + static_cast<size_t>(e) * 8);
         if (!(S.compound && p.x != p.x)) BoundsAddPoint(a, p);   // (a separator is no point)
     }
 }
 
-// The source of Fill or Polyline item i (it: its record)
-__device__ __forceinline__ BoundsSource BoundsSourceOf(const HitParams &P, uint32_t i, const uint8_t *it, uint32_t tag) {
+// The source of a Fill or a Polyline
+__device__ __forceinline__ BoundsSource BoundsSourceOf(const SceneView &V, const ItemHead &h) {
     BoundsSource S;
-    const uint32_t npt = LoadU32(it + 12);
-    S.pts = P.scene + LoadU32(it + 16);
-    S.compound = tag == kItemFill && (LoadU32(it + 4) & kFillCompound) != 0u;
+    const uint32_t i = h.item, tag = h.tag;
+    const uint32_t npt = LoadU32(h.it + 12);
+    S.pts = V.scene + LoadU32(h.it + 16);
+    S.compound = tag == kItemFill && (LoadU32(h.it + 4) & kFillCompound) != 0u;
     S.n = npt;
     if (!S.compound && npt != 0u && !(tag == kItemPoly && npt == 1u)) {
         S.chunks = true;   // (at least one: FillSegs(npt) >= 1, PolySegs(npt) >= 1)
-        S.first = P.chunk_base[i];
-        S.n = P.chunk_base[i + 1u] - S.first;
+        S.first = V.chunk_base[i];
+        S.n = V.chunk_base[i + 1u] - S.first;
     }
     return S;
 }
@@ -149,8 +152,8 @@ __device__ __forceinline__ void BoundsWaveUnion(BoundsAcc &a) {
 }
 
 // The D22 box of item 64 step + lane (mine: there is such an item), and whether the flags skip it.  Called by the whole wave.
-__device__ __forceinline__ BoundsBox BoundsOfStep(const HitParams &P, uint32_t step, uint32_t lane, bool mine, bool &skipped) {
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
+__device__ __forceinline__ BoundsBox BoundsOfStep(const SceneView &V, uint32_t step, uint32_t lane, bool mine, bool &skipped) {
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
     const uint32_t i = step * 64u + lane;
     BoundsBox box;
     BoundsAcc acc;
@@ -158,41 +161,35 @@ __device__ __forceinline__ BoundsBox BoundsOfStep(const HitParams &P, uint32_t s
     bool points = false, big = false;
     skipped = false;
     if (mine) {
-        const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-        const uint32_t w0 = LoadU32(it);
-        const uint32_t tag = w0 & 0xffffu;
-        if (tag == kItemCircle) {
-            const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-            box = BoundsCircle(bb.x & 0xffffu, bb.x >> 16, bb.y & 0xffffu, bb.y >> 16, (w0 & kCircleEllipse) != 0);
-        } else if (tag == kItemLine) {
-            skipped = skip && (LoadU32(it + 8) >> 24) == 0u;
-            hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 12)));
+        const ItemHead h = LoadItemHead(V, i);
+        if (h.tag == kItemCircle) {
+            box = BoundsCircle(h.x0, h.y0, h.x1, h.y1, (h.w0 & kCircleEllipse) != 0);
+        } else if (h.tag == kItemLine) {
+            skipped = skip && ItemTransparent(h);
+            hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(h.it + 12)));
             if (!skipped && hw == hw) {
-                BoundsAddPoint(acc, LoadF2(it + 16));
-                BoundsAddPoint(acc, LoadF2(it + 24));
+                BoundsAddPoint(acc, LoadF2(h.it + 16));
+                BoundsAddPoint(acc, LoadF2(h.it + 24));
                 points = true;
             }
-        } else if (tag == kItemFill || tag == kItemPoly) {
-            skipped = skip && (LoadU32(it + (tag == kItemFill ? 8 : 4)) >> 24) == 0u;
-            if (tag == kItemPoly) hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 8)));
+        } else if (h.tag == kItemFill || h.tag == kItemPoly) {
+            skipped = skip && ItemTransparent(h);
+            if (h.tag == kItemPoly) hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(h.it + 8)));
             if (!skipped && hw == hw) {
-                const BoundsSource S = BoundsSourceOf(P, i, it, tag);
+                const BoundsSource S = BoundsSourceOf(V, h);
                 points = true;
                 big = S.n > kBoundsLane;
                 if (!big)
-                    for (uint32_t e = 0; e < S.n; ++e) BoundsAddEntry(P, S, e, acc);
+                    for (uint32_t e = 0; e < S.n; ++e) BoundsAddEntry(V, S, e, acc);
             }
         }
     }
     uint64_t m = __ballot(big);
     while (m != 0ull) {   // the long items of the step, one after the other, by the whole wave
-        const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-        m &= m - 1ull;
-        const uint32_t ib = step * 64u + l;
-        const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(ib) * kItemSize;
-        const BoundsSource S = BoundsSourceOf(P, ib, it, LoadU32(it) & 0xffffu);
+        const uint32_t l = TakeLowestLane(m);
+        const BoundsSource S = BoundsSourceOf(V, LoadItemHead(V, step * 64u + l));
         BoundsAcc part;
-        for (uint32_t e = lane; e < S.n; e += 64u) BoundsAddEntry(P, S, e, part);
+        for (uint32_t e = lane; e < S.n; e += 64u) BoundsAddEntry(V, S, e, part);
         BoundsWaveUnion(part);
         if (lane == l) acc = part;
     }
@@ -220,15 +217,14 @@ __device__ __forceinline__ double BoundsShfl(double v, int src) {
 }  // namespace
 
 __global__ __launch_bounds__(kHitThreads) void pm_item_bounds_kernel(BoundsParams B) {
-    const HitParams &P = B.H;
+    const SceneView &V = B.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const uint32_t n_steps = (P.n_items + 63u) / 64u;
-    for (uint32_t step = blockIdx.x * kHitWaves + WaveId(); step < n_steps; step += n_waves) {
+    const uint32_t n_waves = GridWaves(), n_steps = ItemSteps(V.n_items);
+    for (uint32_t step = FirstWaveUnit(); step < n_steps; step += n_waves) {
         const uint32_t i = step * 64u + lane;
-        const bool mine = i < P.n_items;
+        const bool mine = i < V.n_items;
         bool skipped;
-        const BoundsBox b = BoundsOfStep(P, step, lane, mine, skipped);
+        const BoundsBox b = BoundsOfStep(V, step, lane, mine, skipped);
         if (mine) {
             double *rec = reinterpret_cast<double *>(B.out + static_cast<size_t>(i) * 32);   // (8-byte aligned)
             rec[0] = b.x0;
@@ -250,15 +246,14 @@ __global__ __launch_bounds__(256) void pm_bounds_init_kernel(uint8_t *out, uint3
 }
 
 __global__ __launch_bounds__(kHitThreads) void pm_union_bounds_kernel(BoundsParams B) {
-    const HitParams &P = B.H;
+    const SceneView &V = B.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const uint32_t n_steps = (P.n_items + 63u) / 64u;
-    for (uint32_t step = blockIdx.x * kHitWaves + WaveId(); step < n_steps; step += n_waves) {
+    const uint32_t n_waves = GridWaves(), n_steps = ItemSteps(V.n_items);
+    for (uint32_t step = FirstWaveUnit(); step < n_steps; step += n_waves) {
         const uint32_t i = step * 64u + lane;
-        const bool mine = i < P.n_items;
+        const bool mine = i < V.n_items;
         bool skipped;
-        BoundsBox b = BoundsOfStep(P, step, lane, mine, skipped);
+        BoundsBox b = BoundsOfStep(V, step, lane, mine, skipped);
         uint32_t label = kBoundsNoLabel;
         if (mine && !skipped && (B.item_words == nullptr || (B.item_words[i] & B.word_mask) != 0u)) {
             label = B.label_of_item != nullptr ? B.label_of_item[i] : 0u;
@@ -314,23 +309,15 @@ __global__ __launch_bounds__(256) void pm_bounds_final_kernel(uint8_t *out, uint
     v[3] = y1;
 }
 
-// grid: a wave per step of 64 items, or what the chip holds at once (eight workgroups of four waves per CU) if that is less
 void LaunchItemBounds(const BoundsParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n_items == 0u) return;
-    const uint32_t n_steps = (p.H.n_items + 63u) / 64u;
-    const uint32_t grid = min((n_steps + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_item_bounds_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
+    LaunchQuery(pm_item_bounds_kernel, p, ItemSteps(p.V.n_items), n_cus, stream);
 }
 
 // the three launches of a union: all n_labels records are written, also of a scene without items
 void LaunchUnionBounds(const BoundsParams &p, uint32_t n_cus, hipStream_t stream) {
     const uint32_t label_grid = (p.n_labels - 1u) / 256u + 1u;   // (n_labels >= 1)
     hipLaunchKernelGGL(pm_bounds_init_kernel, dim3(label_grid), dim3(256), 0, stream, p.out, p.n_labels);
-    if (p.H.n_items != 0u) {
-        const uint32_t n_steps = (p.H.n_items + 63u) / 64u;
-        const uint32_t grid = min((n_steps + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-        hipLaunchKernelGGL(pm_union_bounds_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
-    }
+    LaunchQuery(pm_union_bounds_kernel, p, ItemSteps(p.V.n_items), n_cus, stream);
     hipLaunchKernelGGL(pm_bounds_final_kernel, dim3(label_grid), dim3(256), 0, stream, p.out, p.n_labels);
 }
 

@@ -337,15 +337,14 @@ struct pm_ctx {
     pm::FlattenCache flatten_cache;  // resident paths + scratch of the flatten stage
     bool scene_from_paths = false;   // the resident scene is the flatten kernels' (pm_item_paths maps its items to their paths)
 
-    // point hit testing (pm_hit_test / pm_hit_test_device): reads the scene and the scene index, nothing of a frame
+    // the queries (hit testing, the item map, rectangle and polygon queries, snapping, bounds): they read the scene and the scene
+    // index, nothing of a frame
     hipEvent_t ev_scene = nullptr;     // end of what the last scene replacement left on `stream` (upload, index): a hit test on another stream starts behind it
     hipEvent_t ev_hit = nullptr;       // end of the hit tests submitted so far; a scene replacement waits for it (SyncAll)
     hipStream_t hit_stream = nullptr;  // the stream it was last recorded on (compared, never dereferenced)
     bool hit_pending = false;          // a hit test was submitted since everything was last waited for
-    uint8_t *d_hit = nullptr;          // pm_hit_test's device staging: one batch of {xy, top_item, n_hit}
-    size_t hit_cap = 0;                // queries it holds
-    uint8_t *d_rect = nullptr;         // pm_hit_rects' / pm_select_rect's device staging, a buffer of its own (24 bytes per rectangle query)
-    size_t rect_cap = 0;               // bytes it holds
+    uint8_t *d_stage = nullptr;        // the host-memory queries' device staging (QueryStaging): every such call ends synchronised, so one serves all
+    size_t stage_cap = 0;              // bytes it holds
     // pm_select_polygon's vertices: a ring of slots, each a pinned host buffer, its device copy and the event behind the kernel
     // that last read it.  A call takes the next slot, waits for that event, and copies and launches on its own stream.
     static constexpr int kPolySlots = 4;
@@ -1985,8 +1984,7 @@ void pm_destroy(pm_ctx *c) {
         if (ev) (void)hipEventDestroy(ev);
     if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
     if (c->ev_hit) (void)hipEventDestroy(c->ev_hit);
-    if (c->d_hit) (void)hipFree(c->d_hit);
-    if (c->d_rect) (void)hipFree(c->d_rect);
+    if (c->d_stage) (void)hipFree(c->d_stage);
     for (int k = 0; k < pm_ctx::kPolySlots; ++k) {
         if (c->ev_poly[k]) (void)hipEventDestroy(c->ev_poly[k]);
         if (c->d_poly[k]) (void)hipFree(c->d_poly[k]);
@@ -2854,16 +2852,27 @@ int pm_fill_coverage(pm_ctx *c, uint32_t item_ix, float *dst, size_t dst_stride_
     return status != PM_OK ? status : rb;
 }
 
-// ---- point hit testing (pm_hit_kernel, pm_hit_test.h) ----------------------------------------------------------------
+extern "C++" {
+// ---- the queries' host scaffold (pm_query_common.h) ---------------------------------------------------------------------------
+// (Templates: the block has C++ linkage inside the C interface.)  Every query call is: its check, QueryOrderBefore, its launches with a QueryView, QueryOrderBehind; a host-memory variant stages
+// through QueryStaging and ends with a synchronisation of c->stream.
 namespace {
-constexpr size_t kHitLaunchMax = static_cast<size_t>(1) << 30;  // queries per launch (the kernel indexes them in 32 bits)
-constexpr size_t kHitBatch = static_cast<size_t>(1) << 22;      // pm_hit_test: queries staged on the device at a time (64 MiB)
+constexpr size_t kHitLaunchMax = static_cast<size_t>(1) << 30;  // queries per launch (the kernels index them in 32 bits)
+constexpr size_t kHitBatch = static_cast<size_t>(1) << 22;      // pm_hit_test, pm_hit_frame: queries staged on the device at a time (64 MiB)
+constexpr size_t kRectBatch = static_cast<size_t>(1) << 20;     // pm_hit_rects, pm_snap, pm_snap_intersections: the same (24 to 60 MiB)
 
-int HitCheck(pm_ctx *c, uint32_t flags) {
-    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)) {
-        SetError("pm_hit_test: unknown flag bits");
-        return PM_ERR_INVALID;
-    }
+static_assert(PM_HIT_SKIP_TRANSPARENT == pm::kHitSkipTransparent && PM_HIT_NONE == pm::kHitNone && PM_SEL_TOUCHES == pm::kSelTouches &&
+                  PM_SEL_ENCLOSES == pm::kSelEncloses && PM_POLYGON_MAX_VERTICES == pm::kPolyMaxVertices,
+              "pm_query_common.h's and pm_hit_poly.h's constants are the header's");
+static_assert(PM_SNAP_VERTICES == pm::kSnapVertices && PM_SNAP_EDGES == pm::kSnapEdges && PM_SNAP_KIND_VERTEX == pm::kSnapKindVertex &&
+                  PM_SNAP_KIND_EDGE == pm::kSnapKindEdge,
+              "pm_snap.h's constants are the header's");
+static_assert(PM_SNAP_MAX_NEAR_EDGES == pm::kCrossMaxNear && PM_SNAP_KIND_INTERSECTION == pm::kSnapKindIntersection && PM_SNAP_KIND_TOO_MANY == pm::kSnapKindTooMany,
+              "pm_snap_cross.h's constants are the header's");
+
+hipStream_t QueryStream(pm_ctx *c, void *hip_stream) { return hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream; }
+
+int SceneResident(pm_ctx *c) {
     if (!c->d_scene || c->scene_bytes < 8) {  // (what pm_render says: BuildParams)
         SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
         return PM_ERR_INVALID;
@@ -2871,28 +2880,38 @@ int HitCheck(pm_ctx *c, uint32_t flags) {
     return PM_OK;
 }
 
-// The launches for n queries in device memory, on q.  They read the scene buffer and the scene index as they are now: whatever
-// replaces them waits for ev_hit first (SyncAll).
-int HitEnqueue(pm_ctx *c, const float *d_xy, size_t n, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, hipStream_t q) {
-    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));  // the scene's upload and index ran on c->stream
-    // (ONE event stands for every hit test submitted: when it moves to another stream, that stream first waits for what it stood for)
-    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
-    pm::HitParams p{};
-    p.scene = c->d_scene;
-    p.n_items = c->n_items;
-    p.items_ix = c->dev_items_ix;
-    p.bbox_ix = c->dev_bbox_ix;
-    p.chunk_base = c->d_chunk_base;
-    p.chunk_bbox = c->d_chunk_bbox;
-    p.sup_bbox = c->d_sup_bbox;
-    p.flags = flags;
-    for (size_t at = 0; at < n; at += kHitLaunchMax) {
-        p.xy = d_xy + 2 * at;
-        p.top_item = d_top + at;
-        p.n_hit = d_cnt ? d_cnt + at : nullptr;
-        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
-        pm::LaunchHitTest(p, static_cast<uint32_t>(c->n_cus), q);
+int HitCheck(pm_ctx *c, uint32_t flags) {
+    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)) {
+        SetError("pm_hit_test: unknown flag bits");
+        return PM_ERR_INVALID;
     }
+    return SceneResident(c);
+}
+
+// What a kernel reads of the context: the scene and the scene index as they are now, and the call's flags
+pm::SceneView QueryView(pm_ctx *c, uint32_t flags) {
+    pm::SceneView v{};
+    v.scene = c->d_scene;
+    v.n_items = c->n_items;
+    v.items_ix = c->dev_items_ix;
+    v.bbox_ix = c->dev_bbox_ix;
+    v.chunk_base = c->d_chunk_base;
+    v.chunk_bbox = c->d_chunk_bbox;
+    v.sup_bbox = c->d_sup_bbox;
+    v.flags = flags;
+    return v;
+}
+
+// The ordering rule of every query, for launches on q.  Before them: q waits for ev_scene unless it is c->stream (the scene's upload
+// and index ran there), and for ev_hit if the queries submitted so far went to another stream (ONE event stands for every query
+// submitted: when it moves to another stream, that stream first waits for what it stood for) ...
+int QueryOrderBefore(pm_ctx *c, hipStream_t q) {
+    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));
+    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
+    return PM_OK;
+}
+// ... and behind them ev_hit: whatever replaces the scene buffer or the scene index waits for it first (SyncAll)
+int QueryOrderBehind(pm_ctx *c, hipStream_t q) {
     PM_TRY(hipGetLastError());
     PM_TRY(hipEventRecord(c->ev_hit, q));
     c->hit_stream = q;
@@ -2900,18 +2919,148 @@ int HitEnqueue(pm_ctx *c, const float *d_xy, size_t n, uint32_t flags, uint32_t 
     return PM_OK;
 }
 
-// c->d_hit holds `batch` queries: {xy, top_item, n_hit}, 16 bytes each (pm_hit_frame uses the last two)
-hipError_t HitStaging(pm_ctx *c, size_t batch) {
-    if (batch <= c->hit_cap) return hipSuccess;
+// c->d_stage holds `bytes` bytes, laid out by the call that asked.  Grow-only; nothing on c->stream uses the old buffer when it is freed.
+hipError_t QueryStaging(pm_ctx *c, size_t bytes) {
+    if (bytes <= c->stage_cap) return hipSuccess;
     hipError_t e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return e;
-    if (c->d_hit) (void)hipFree(c->d_hit);
-    c->d_hit = nullptr;
-    c->hit_cap = 0;
-    e = hipMalloc(&c->d_hit, batch * 16);
+    if (c->d_stage) (void)hipFree(c->d_stage);
+    c->d_stage = nullptr;
+    c->stage_cap = 0;
+    e = hipMalloc(&c->d_stage, bytes);
     if (e != hipSuccess) return e;
-    c->hit_cap = batch;
+    c->stage_cap = bytes;
     return hipSuccess;
+}
+
+// Where a host-memory call's records go: `bytes` per query (host = nullptr: not asked for)
+struct QueryOut {
+    void *host;
+    size_t bytes;
+};
+
+// n queries of in_bytes each in host memory, batch_max at a time through the staging buffer, laid out {out0, out1, queries, prefix}:
+// the prefix (a call's per-item words) is uploaded once, then batch by batch the queries go up, enqueue(d_in, m, d_out0, d_out1,
+// d_prefix) submits the m of them on c->stream, and the records come back.  d_out1 / d_prefix are nullptr if there is none.
+template <typename Enqueue>
+int QueryBatches(pm_ctx *c, const void *in, size_t in_bytes, size_t n, size_t batch_max, QueryOut out0, QueryOut out1, const void *prefix, size_t prefix_bytes,
+                 Enqueue &&enqueue) {
+    const size_t batch = std::min(n, batch_max);
+    const size_t at_out1 = batch * out0.bytes, at_in = at_out1 + batch * out1.bytes, at_prefix = at_in + batch * in_bytes;
+    PM_TRY(QueryStaging(c, at_prefix + prefix_bytes));
+    uint8_t *d_out0 = c->d_stage, *d_out1 = out1.host ? c->d_stage + at_out1 : nullptr, *d_in = c->d_stage + at_in;
+    uint8_t *d_prefix = prefix_bytes ? c->d_stage + at_prefix : nullptr;
+    if (prefix_bytes) PM_TRY(hipMemcpyAsync(d_prefix, prefix, prefix_bytes, hipMemcpyHostToDevice, c->stream));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(d_in, static_cast<const uint8_t *>(in) + at * in_bytes, m * in_bytes, hipMemcpyHostToDevice, c->stream));
+        const int r = enqueue(d_in, m, d_out0, d_out1, d_prefix);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(static_cast<uint8_t *>(out0.host) + at * out0.bytes, d_out0, m * out0.bytes, hipMemcpyDeviceToHost, c->stream));
+        if (d_out1) PM_TRY(hipMemcpyAsync(static_cast<uint8_t *>(out1.host) + at * out1.bytes, d_out1, m * out1.bytes, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+// What pm_select_rect and pm_select_polygon do once the call's own arguments are checked: a word per item through the staging
+// buffer -- enqueue(d_flags) submits on c->stream -- and the two counts
+template <typename Enqueue>
+int SelectToHost(pm_ctx *c, uint32_t *item_flags, size_t cap, uint32_t *n_touched, uint32_t *n_enclosed, Enqueue &&enqueue) {
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n != 0 && !item_flags) return PM_ERR_INVALID;
+    if (n != 0) {
+        PM_TRY(QueryStaging(c, n * 4));
+        const int r = enqueue(reinterpret_cast<uint32_t *>(c->d_stage));
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(item_flags, c->d_stage, n * 4, hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    uint32_t touched = 0, enclosed = 0;
+    for (size_t i = 0; i < n; ++i) {
+        touched += (item_flags[i] & PM_SEL_TOUCHES) ? 1u : 0u;
+        enclosed += (item_flags[i] & PM_SEL_ENCLOSES) ? 1u : 0u;
+    }
+    if (n_touched) *n_touched = touched;
+    if (n_enclosed) *n_enclosed = enclosed;
+    return PM_OK;
+}
+
+static_assert(sizeof(pm_snap_result) == 32 && offsetof(pm_snap_result, item) == 0 && offsetof(pm_snap_result, kind) == 4 &&
+                  offsetof(pm_snap_result, index) == 8 && offsetof(pm_snap_result, t) == 12 && offsetof(pm_snap_result, x) == 16 &&
+                  offsetof(pm_snap_result, y) == 20 && offsetof(pm_snap_result, d2) == 24,
+              "the record pm_snap_kernel writes");
+static_assert(sizeof(pm_snap_cross_result) == 48 && offsetof(pm_snap_cross_result, item) == 0 && offsetof(pm_snap_cross_result, kind) == 4 &&
+                  offsetof(pm_snap_cross_result, index) == 8 && offsetof(pm_snap_cross_result, t) == 12 && offsetof(pm_snap_cross_result, x) == 16 &&
+                  offsetof(pm_snap_cross_result, y) == 20 && offsetof(pm_snap_cross_result, d2) == 24 && offsetof(pm_snap_cross_result, item2) == 32 &&
+                  offsetof(pm_snap_cross_result, index2) == 36 && offsetof(pm_snap_cross_result, u) == 40 && offsetof(pm_snap_cross_result, n_near) == 44,
+              "the record pm_cross_kernel writes");
+
+// Everything a snapping call refuses, before anything is enqueued.  name: the call's; allowed: its flag bits; kinds: PM_SNAP_VERTICES |
+// PM_SNAP_EDGES if it needs one of them, 0 if it has no such choice
+int SnapCheck(pm_ctx *c, const char *name, uint32_t allowed, uint32_t kinds, const void *xyr, size_t n, uint32_t flags, const void *skip_items, size_t n_skip,
+              const void *out) {
+    auto refuse = [name](const char *why) {
+        SetError(std::string(name) + why);
+        return PM_ERR_INVALID;
+    };
+    if (flags & ~allowed) return refuse(": unknown flag bits");
+    if (kinds && !(flags & kinds)) return refuse(": PM_SNAP_VERTICES, PM_SNAP_EDGES or both");
+    const int r = SceneResident(c);
+    if (r != PM_OK) return r;
+    if (skip_items ? n_skip < c->n_items : n_skip != 0) return refuse(": skip_items holds one word per item, or is NULL with n_skip == 0");
+    if (n != 0 && (!xyr || !out)) return refuse(": a NULL pointer with n != 0");
+    return PM_OK;
+}
+constexpr uint32_t kSnapKinds = PM_SNAP_VERTICES | PM_SNAP_EDGES;
+
+// The launches of either kernel for n queries in device memory, on q: their params differ in the record's size alone
+template <typename Params>
+int SnapEnqueue(pm_ctx *c, void (*launch)(const Params &, uint32_t, hipStream_t), size_t record, const float *d_xyr, size_t n, uint32_t flags,
+                const uint32_t *d_skip, uint8_t *d_out, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    Params p{};
+    p.V = QueryView(c, flags);
+    p.skip_items = d_skip;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.xyr = d_xyr + 3 * at;
+        p.out = d_out + record * at;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        launch(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+
+// The host-memory variant of either: {records, queries, skip words} through the staging buffer
+template <typename Params>
+int SnapToHost(pm_ctx *c, void (*launch)(const Params &, uint32_t, hipStream_t), size_t record, const float *xyr, size_t n, uint32_t flags,
+               const uint32_t *skip_items, void *out) {
+    return QueryBatches(c, xyr, 12, n, kRectBatch, {out, record}, {nullptr, 0}, skip_items, skip_items ? static_cast<size_t>(c->n_items) * 4 : 0,
+                        [&](uint8_t *d_in, size_t m, uint8_t *d_out, uint8_t *, uint8_t *d_skip) {
+                            return SnapEnqueue(c, launch, record, reinterpret_cast<float *>(d_in), m, flags, reinterpret_cast<uint32_t *>(d_skip), d_out, c->stream);
+                        });
+}
+}  // namespace
+}  // extern "C++"
+
+// ---- point hit testing (pm_hit_kernel, pm_hit_test.h) ----------------------------------------------------------------
+namespace {
+// The launches for n queries in device memory, on q.  They read the scene buffer and the scene index as they are now.
+int HitEnqueue(pm_ctx *c, const float *d_xy, size_t n, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::HitParams p{};
+    p.V = QueryView(c, flags);
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.xy = d_xy + 2 * at;
+        p.top_item = d_top + at;
+        p.n_hit = d_cnt ? d_cnt + at : nullptr;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchHitTest(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
 }
 
 // What both item-map calls refuse, before anything is enqueued
@@ -2933,19 +3082,13 @@ int HitFrameCheck(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, u
     return PM_OK;
 }
 
-// The launch for a rectangle, on q: HitEnqueue's ordering (ev_scene before, ev_hit behind), pm_hit_frame_kernel in between.
+// The launch for a rectangle of pixels, on q
 int HitFrameEnqueue(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, size_t stride,
                     hipStream_t q) {
-    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));
-    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
     pm::HitFrameParams p{};
-    p.scene = c->d_scene;
-    p.n_items = c->n_items;
-    p.items_ix = c->dev_items_ix;
-    p.bbox_ix = c->dev_bbox_ix;
-    p.chunk_base = c->d_chunk_base;
-    p.chunk_bbox = c->d_chunk_bbox;
-    p.sup_bbox = c->d_sup_bbox;
+    p.V = QueryView(c, flags);
     p.top_item = d_top;
     p.n_hit = d_cnt;
     p.stride = stride;
@@ -2953,13 +3096,8 @@ int HitFrameEnqueue(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h,
     p.y0 = y0;
     p.w = w;
     p.h = h;
-    p.flags = flags;
     pm::LaunchHitFrame(p, static_cast<uint32_t>(c->n_cus), q);
-    PM_TRY(hipGetLastError());
-    PM_TRY(hipEventRecord(c->ev_hit, q));
-    c->hit_stream = q;
-    c->hit_pending = true;
-    return PM_OK;
+    return QueryOrderBehind(c, q);
 }
 }  // namespace
 
@@ -2969,29 +3107,17 @@ int pm_hit_test_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t flags, 
     const int r = HitCheck(c, flags);
     if (r != PM_OK || n == 0) return r;
     return HitEnqueue(c, static_cast<const float *>(dev_xy), n, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit),
-                      hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+                      QueryStream(c, hip_stream));
 }
 
 int pm_hit_test(pm_ctx *c, const float *xy, size_t n, uint32_t flags, uint32_t *top_item, uint32_t *n_hit) {
     if (!c || (n != 0 && (!xy || !top_item))) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    int r = HitCheck(c, flags);
+    const int r = HitCheck(c, flags);
     if (r != PM_OK || n == 0) return r;
-    const size_t batch = std::min(n, kHitBatch);
-    PM_TRY(HitStaging(c, batch));
-    float *d_xy = reinterpret_cast<float *>(c->d_hit);
-    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_hit + c->hit_cap * 8);
-    uint32_t *d_cnt = n_hit ? d_top + c->hit_cap : nullptr;
-    for (size_t at = 0; at < n; at += batch) {
-        const size_t m = std::min(batch, n - at);
-        PM_TRY(hipMemcpyAsync(d_xy, xy + 2 * at, m * 8, hipMemcpyHostToDevice, c->stream));
-        r = HitEnqueue(c, d_xy, m, flags, d_top, d_cnt, c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(top_item + at, d_top, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (n_hit) PM_TRY(hipMemcpyAsync(n_hit + at, d_cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    return PM_OK;
+    return QueryBatches(c, xy, 8, n, kHitBatch, {top_item, 4}, {n_hit, 4}, nullptr, 0, [&](uint8_t *d_in, size_t m, uint8_t *d_top, uint8_t *d_cnt, uint8_t *) {
+        return HitEnqueue(c, reinterpret_cast<float *>(d_in), m, flags, reinterpret_cast<uint32_t *>(d_top), reinterpret_cast<uint32_t *>(d_cnt), c->stream);
+    });
 }
 
 // ---- the item map (pm_hit_frame_kernel, pm_hit_frame.h) -----------------------------------------------------------------
@@ -3001,8 +3127,7 @@ int pm_hit_frame_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_
     PM_TRY(hipSetDevice(c->device));
     const int r = HitFrameCheck(c, x0, y0, w, h, flags, dev_top_item, stride);
     if (r != PM_OK || w == 0 || h == 0) return r;
-    return HitFrameEnqueue(c, x0, y0, w, h, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit), stride,
-                           hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return HitFrameEnqueue(c, x0, y0, w, h, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit), stride, QueryStream(c, hip_stream));
 }
 
 int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, uint32_t *top_item, uint32_t *n_hit, size_t stride) {
@@ -3010,11 +3135,11 @@ int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, ui
     PM_TRY(hipSetDevice(c->device));
     int r = HitFrameCheck(c, x0, y0, w, h, flags, top_item, stride);
     if (r != PM_OK || w == 0 || h == 0) return r;
-    // batches of whole rows, dense on the device (a multiple of the tile's height, so that a batch's tiles are the rectangle's)
+    // batches of whole rows, dense on the device (a multiple of the tile's height, so that a batch's tiles are the rectangle's): {top_item, n_hit}
     const size_t rows = std::min<size_t>(h, std::max<size_t>(kHitBatch / w / 16, 1) * 16);
-    PM_TRY(HitStaging(c, rows * w));
-    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_hit + c->hit_cap * 8);
-    uint32_t *d_cnt = n_hit ? d_top + c->hit_cap : nullptr;
+    PM_TRY(QueryStaging(c, rows * w * 8));
+    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_stage);
+    uint32_t *d_cnt = n_hit ? d_top + rows * w : nullptr;
     for (size_t at = 0; at < h; at += rows) {
         const size_t m = std::min<size_t>(rows, h - at);
         r = HitFrameEnqueue(c, x0, y0 + static_cast<uint32_t>(at), w, static_cast<uint32_t>(m), flags, d_top, d_cnt, w, c->stream);
@@ -3028,73 +3153,30 @@ int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, ui
 
 // ---- rectangle queries (pm_hit_rects_kernel, pm_select_rect_kernel, pm_hit_rect.h; decision D19) ---------------------------
 namespace {
-constexpr size_t kRectBatch = static_cast<size_t>(1) << 20;  // pm_hit_rects: queries staged on the device at a time (24 MiB)
-
-// What the two kernels read of the context: the scene, its index and the flags
-pm::HitRectParams RectParams(pm_ctx *c, uint32_t flags) {
-    pm::HitRectParams p{};
-    p.H.scene = c->d_scene;
-    p.H.n_items = c->n_items;
-    p.H.items_ix = c->dev_items_ix;
-    p.H.bbox_ix = c->dev_bbox_ix;
-    p.H.chunk_base = c->d_chunk_base;
-    p.H.chunk_bbox = c->d_chunk_bbox;
-    p.H.sup_bbox = c->d_sup_bbox;
-    p.H.flags = flags;
-    return p;
-}
-
-// HitEnqueue's ordering for a launch on q: behind ev_scene and, on another stream than the last, behind ev_hit ...
-int RectOrderBefore(pm_ctx *c, hipStream_t q) {
-    if (q != c->stream) PM_TRY(hipStreamWaitEvent(q, c->ev_scene, 0));
-    if (c->hit_pending && c->hit_stream != q) PM_TRY(hipStreamWaitEvent(q, c->ev_hit, 0));
-    return PM_OK;
-}
-// ... and ev_hit behind it: whatever replaces the scene waits for it first (SyncAll)
-int RectOrderBehind(pm_ctx *c, hipStream_t q) {
-    PM_TRY(hipGetLastError());
-    PM_TRY(hipEventRecord(c->ev_hit, q));
-    c->hit_stream = q;
-    c->hit_pending = true;
-    return PM_OK;
-}
-
 int HitRectsEnqueue(pm_ctx *c, const float *d_rects, size_t n, uint32_t flags, uint32_t *d_top, uint32_t *d_cnt, hipStream_t q) {
-    int r = RectOrderBefore(c, q);
+    int r = QueryOrderBefore(c, q);
     if (r != PM_OK) return r;
-    pm::HitRectParams p = RectParams(c, flags);
+    pm::HitRectParams p{};
+    p.V = QueryView(c, flags);
     for (size_t at = 0; at < n; at += kHitLaunchMax) {
         p.rects = d_rects + 4 * at;
-        p.H.top_item = d_top + at;
-        p.H.n_hit = d_cnt ? d_cnt + at : nullptr;
-        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        p.top_item = d_top + at;
+        p.n_hit = d_cnt ? d_cnt + at : nullptr;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
         pm::LaunchHitRects(p, static_cast<uint32_t>(c->n_cus), q);
     }
-    return RectOrderBehind(c, q);
+    return QueryOrderBehind(c, q);
 }
 
 int SelectRectEnqueue(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *d_flags, hipStream_t q) {
-    int r = RectOrderBefore(c, q);
+    int r = QueryOrderBefore(c, q);
     if (r != PM_OK) return r;
-    pm::HitRectParams p = RectParams(c, flags);
+    pm::SelectRectParams p{};
+    p.V = QueryView(c, flags);
     std::memcpy(p.rect, rect, sizeof(p.rect));
     p.item_flags = d_flags;
     pm::LaunchSelectRect(p, static_cast<uint32_t>(c->n_cus), q);
-    return RectOrderBehind(c, q);
-}
-
-// c->d_rect holds `bytes` bytes
-hipError_t RectStaging(pm_ctx *c, size_t bytes) {
-    if (bytes <= c->rect_cap) return hipSuccess;
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return e;
-    if (c->d_rect) (void)hipFree(c->d_rect);
-    c->d_rect = nullptr;
-    c->rect_cap = 0;
-    e = hipMalloc(&c->d_rect, bytes);
-    if (e != hipSuccess) return e;
-    c->rect_cap = bytes;
-    return hipSuccess;
+    return QueryOrderBehind(c, q);
 }
 }  // namespace
 
@@ -3104,29 +3186,17 @@ int pm_hit_rects_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t fla
     const int r = HitCheck(c, flags);
     if (r != PM_OK || n == 0) return r;
     return HitRectsEnqueue(c, static_cast<const float *>(dev_rects), n, flags, static_cast<uint32_t *>(dev_top_item), static_cast<uint32_t *>(dev_n_hit),
-                           hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+                           QueryStream(c, hip_stream));
 }
 
 int pm_hit_rects(pm_ctx *c, const float *rects, size_t n, uint32_t flags, uint32_t *top_item, uint32_t *n_hit) {
     if (!c || (n != 0 && (!rects || !top_item))) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    int r = HitCheck(c, flags);
+    const int r = HitCheck(c, flags);
     if (r != PM_OK || n == 0) return r;
-    const size_t batch = std::min(n, kRectBatch);
-    PM_TRY(RectStaging(c, batch * 24));   // {rect, top_item, n_hit}
-    float *d_rects = reinterpret_cast<float *>(c->d_rect);
-    uint32_t *d_top = reinterpret_cast<uint32_t *>(c->d_rect + batch * 16);
-    uint32_t *d_cnt = n_hit ? d_top + batch : nullptr;
-    for (size_t at = 0; at < n; at += batch) {
-        const size_t m = std::min(batch, n - at);
-        PM_TRY(hipMemcpyAsync(d_rects, rects + 4 * at, m * 16, hipMemcpyHostToDevice, c->stream));
-        r = HitRectsEnqueue(c, d_rects, m, flags, d_top, d_cnt, c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(top_item + at, d_top, m * 4, hipMemcpyDeviceToHost, c->stream));
-        if (n_hit) PM_TRY(hipMemcpyAsync(n_hit + at, d_cnt, m * 4, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    return PM_OK;
+    return QueryBatches(c, rects, 16, n, kRectBatch, {top_item, 4}, {n_hit, 4}, nullptr, 0, [&](uint8_t *d_in, size_t m, uint8_t *d_top, uint8_t *d_cnt, uint8_t *) {
+        return HitRectsEnqueue(c, reinterpret_cast<float *>(d_in), m, flags, reinterpret_cast<uint32_t *>(d_top), reinterpret_cast<uint32_t *>(d_cnt), c->stream);
+    });
 }
 
 int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream) {
@@ -3137,7 +3207,7 @@ int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *
     if (cap < c->n_items) return PM_ERR_CAPACITY;
     if (c->n_items == 0) return PM_OK;
     if (!dev_item_flags) return PM_ERR_INVALID;
-    return SelectRectEnqueue(c, rect, flags, static_cast<uint32_t *>(dev_item_flags), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return SelectRectEnqueue(c, rect, flags, static_cast<uint32_t *>(dev_item_flags), QueryStream(c, hip_stream));
 }
 
 int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *item_flags, size_t cap, uint32_t *n_items, uint32_t *n_touched,
@@ -3146,33 +3216,15 @@ int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *ite
     if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
     if (!rect) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    int r = HitCheck(c, flags);
+    const int r = HitCheck(c, flags);
     if (r != PM_OK) return r;
-    const size_t n = c->n_items;
-    if (cap < n) return PM_ERR_CAPACITY;
-    if (n != 0 && !item_flags) return PM_ERR_INVALID;
-    if (n != 0) {
-        PM_TRY(RectStaging(c, n * 4));
-        r = SelectRectEnqueue(c, rect, flags, reinterpret_cast<uint32_t *>(c->d_rect), c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(item_flags, c->d_rect, n * 4, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    uint32_t touched = 0, enclosed = 0;
-    for (size_t i = 0; i < n; ++i) {
-        touched += (item_flags[i] & PM_SEL_TOUCHES) ? 1u : 0u;
-        enclosed += (item_flags[i] & PM_SEL_ENCLOSES) ? 1u : 0u;
-    }
-    if (n_touched) *n_touched = touched;
-    if (n_enclosed) *n_enclosed = enclosed;
-    return PM_OK;
+    return SelectToHost(c, item_flags, cap, n_touched, n_enclosed, [&](uint32_t *d_flags) { return SelectRectEnqueue(c, rect, flags, d_flags, c->stream); });
 }
 
 // ---- polygon queries (pm_select_polygon_kernel, pm_hit_poly.h; decision D20) -------------------------------------------------
 namespace {
-constexpr size_t kPolyGroupEdges = 16;   // kPolyGroup (pm_hit_poly.h)
 constexpr size_t kPolyVertBytes = static_cast<size_t>(PM_POLYGON_MAX_VERTICES) * 8;
-constexpr size_t kPolyBytes = kPolyVertBytes + PM_POLYGON_MAX_VERTICES / kPolyGroupEdges * 16;   // the vertices, then a box per group of edges
+constexpr size_t kPolyBytes = kPolyVertBytes + PM_POLYGON_MAX_VERTICES / pm::kPolyGroup * 16;   // the vertices, then a box per group of edges
 
 // The ring's buffers, made once at the first polygon query
 hipError_t PolyRing(pm_ctx *c) {
@@ -3197,18 +3249,19 @@ int PolyCheck(pm_ctx *c, const float *xy, size_t m, uint32_t flags) {
 // The launch for a polygon in host memory, on q.  The vertices have left xy when this returns: they are in the slot's pinned
 // buffer, which nothing writes again before the event behind this call's kernel has passed.
 int SelectPolygonEnqueue(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint32_t *d_flags, hipStream_t q) {
+    constexpr size_t kGroup = pm::kPolyGroup;
     PM_TRY(PolyRing(c));
     const uint32_t slot = c->poly_next;
     c->poly_next = (slot + 1u) % pm_ctx::kPolySlots;
     if (c->poly_used[slot]) PM_TRY(hipEventSynchronize(c->ev_poly[slot]));
     std::memcpy(c->h_poly[slot], xy, m * 8);
     float *gb = c->h_poly[slot] + kPolyVertBytes / 4;
-    const size_t n_groups = (m + kPolyGroupEdges - 1) / kPolyGroupEdges;
+    const size_t n_groups = (m + kGroup - 1) / kGroup;
     for (size_t g = 0; g < n_groups; ++g) {   // the ends of edges g * 16 ..: vertices g * 16 .. one past the group's last, mod m
         float *b = gb + 4 * g;
-        b[0] = b[2] = xy[2 * (g * kPolyGroupEdges)];
-        b[1] = b[3] = xy[2 * (g * kPolyGroupEdges) + 1];
-        for (size_t j = g * kPolyGroupEdges; j <= std::min((g + 1) * kPolyGroupEdges, m); ++j) {
+        b[0] = b[2] = xy[2 * (g * kGroup)];
+        b[1] = b[3] = xy[2 * (g * kGroup) + 1];
+        for (size_t j = g * kGroup; j <= std::min((g + 1) * kGroup, m); ++j) {
             const float x = xy[2 * (j % m)], y = xy[2 * (j % m) + 1];
             b[0] = std::min(b[0], x);
             b[1] = std::min(b[1], y);
@@ -3217,7 +3270,7 @@ int SelectPolygonEnqueue(pm_ctx *c, const float *xy, size_t m, uint32_t flags, u
         }
     }
     pm::HitPolyParams p{};
-    p.H = RectParams(c, flags & static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)).H;
+    p.V = QueryView(c, flags & static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT));
     p.verts = c->d_poly[slot];
     p.boxes = c->d_poly[slot] + kPolyVertBytes / 4;
     p.m = static_cast<uint32_t>(m);
@@ -3234,12 +3287,12 @@ int SelectPolygonEnqueue(pm_ctx *c, const float *xy, size_t m, uint32_t flags, u
         p.box[3] = std::max(p.box[3], y);
     }
     p.item_flags = d_flags;
-    int r = RectOrderBefore(c, q);
+    int r = QueryOrderBefore(c, q);
     if (r != PM_OK) return r;
     PM_TRY(hipMemcpyAsync(c->d_poly[slot], c->h_poly[slot], m * 8, hipMemcpyHostToDevice, q));
     PM_TRY(hipMemcpyAsync(c->d_poly[slot] + kPolyVertBytes / 4, gb, n_groups * 16, hipMemcpyHostToDevice, q));
     pm::LaunchSelectPolygon(p, static_cast<uint32_t>(c->n_cus), q);
-    r = RectOrderBehind(c, q);
+    r = QueryOrderBehind(c, q);
     if (r != PM_OK) return r;
     PM_TRY(hipEventRecord(c->ev_poly[slot], q));
     c->poly_used[slot] = true;
@@ -3255,7 +3308,7 @@ int pm_select_polygon_device(pm_ctx *c, const float *xy, size_t m, uint32_t flag
     if (cap < c->n_items) return PM_ERR_CAPACITY;
     if (c->n_items == 0) return PM_OK;
     if (!dev_item_flags) return PM_ERR_INVALID;
-    return SelectPolygonEnqueue(c, xy, m, flags, static_cast<uint32_t *>(dev_item_flags), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return SelectPolygonEnqueue(c, xy, m, flags, static_cast<uint32_t *>(dev_item_flags), QueryStream(c, hip_stream));
 }
 
 int pm_select_polygon(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint32_t *item_flags, size_t cap, uint32_t *n_items, uint32_t *n_touched,
@@ -3263,188 +3316,45 @@ int pm_select_polygon(pm_ctx *c, const float *xy, size_t m, uint32_t flags, uint
     if (!c) return PM_ERR_INVALID;
     if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
     PM_TRY(hipSetDevice(c->device));
-    int r = PolyCheck(c, xy, m, flags);
+    const int r = PolyCheck(c, xy, m, flags);
     if (r != PM_OK) return r;
-    const size_t n = c->n_items;
-    if (cap < n) return PM_ERR_CAPACITY;
-    if (n != 0 && !item_flags) return PM_ERR_INVALID;
-    if (n != 0) {
-        PM_TRY(RectStaging(c, n * 4));
-        r = SelectPolygonEnqueue(c, xy, m, flags, reinterpret_cast<uint32_t *>(c->d_rect), c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(item_flags, c->d_rect, n * 4, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    uint32_t touched = 0, enclosed = 0;
-    for (size_t i = 0; i < n; ++i) {
-        touched += (item_flags[i] & PM_SEL_TOUCHES) ? 1u : 0u;
-        enclosed += (item_flags[i] & PM_SEL_ENCLOSES) ? 1u : 0u;
-    }
-    if (n_touched) *n_touched = touched;
-    if (n_enclosed) *n_enclosed = enclosed;
-    return PM_OK;
+    return SelectToHost(c, item_flags, cap, n_touched, n_enclosed, [&](uint32_t *d_flags) { return SelectPolygonEnqueue(c, xy, m, flags, d_flags, c->stream); });
 }
 
-// ---- snapping (pm_snap_kernel, pm_snap.h; decision D21) ------------------------------------------------------------------------
-namespace {
-static_assert(sizeof(pm_snap_result) == 32 && offsetof(pm_snap_result, item) == 0 && offsetof(pm_snap_result, kind) == 4 &&
-                  offsetof(pm_snap_result, index) == 8 && offsetof(pm_snap_result, t) == 12 && offsetof(pm_snap_result, x) == 16 &&
-                  offsetof(pm_snap_result, y) == 20 && offsetof(pm_snap_result, d2) == 24,
-              "the record pm_snap_kernel writes");
-
-// Everything pm_snap / pm_snap_device refuse, before anything is enqueued
-int SnapCheck(pm_ctx *c, const void *xyr, size_t n, uint32_t flags, const void *skip_items, size_t n_skip, const void *out) {
-    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT | PM_SNAP_VERTICES | PM_SNAP_EDGES)) {
-        SetError("pm_snap: unknown flag bits");
-        return PM_ERR_INVALID;
-    }
-    if (!(flags & (PM_SNAP_VERTICES | PM_SNAP_EDGES))) {
-        SetError("pm_snap: PM_SNAP_VERTICES, PM_SNAP_EDGES or both");
-        return PM_ERR_INVALID;
-    }
-    if (!c->d_scene || c->scene_bytes < 8) {
-        SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
-        return PM_ERR_INVALID;
-    }
-    if (skip_items ? n_skip < c->n_items : n_skip != 0) {
-        SetError("pm_snap: skip_items holds one word per item, or is NULL with n_skip == 0");
-        return PM_ERR_INVALID;
-    }
-    if (n != 0 && (!xyr || !out)) {
-        SetError("pm_snap: a NULL pointer with n != 0");
-        return PM_ERR_INVALID;
-    }
-    return PM_OK;
-}
-
-// HitRectsEnqueue's ordering (ev_scene before, ev_hit behind), pm_snap_kernel in between
-int SnapEnqueue(pm_ctx *c, const float *d_xyr, size_t n, uint32_t flags, const uint32_t *d_skip, uint8_t *d_out, hipStream_t q) {
-    int r = RectOrderBefore(c, q);
-    if (r != PM_OK) return r;
-    pm::SnapParams p{};
-    p.H = RectParams(c, flags).H;
-    p.skip_items = d_skip;
-    for (size_t at = 0; at < n; at += kHitLaunchMax) {
-        p.xyr = d_xyr + 3 * at;
-        p.out = d_out + 32 * at;
-        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
-        pm::LaunchSnap(p, static_cast<uint32_t>(c->n_cus), q);
-    }
-    return RectOrderBehind(c, q);
-}
-}  // namespace
-
+// ---- snapping (pm_snap_kernel, pm_snap.h; decision D21) and snapping to intersections (pm_cross_kernel, pm_snap_cross.h; D23) ----------
 int pm_snap_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags, const void *dev_skip_items, size_t n_skip, void *dev_out, void *hip_stream) {
     if (!c) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    const int r = SnapCheck(c, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
+    const int r = SnapCheck(c, "pm_snap", PM_HIT_SKIP_TRANSPARENT | kSnapKinds, kSnapKinds, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
     if (r != PM_OK || n == 0) return r;
-    return SnapEnqueue(c, static_cast<const float *>(dev_xyr), n, flags, static_cast<const uint32_t *>(dev_skip_items), static_cast<uint8_t *>(dev_out),
-                       hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return SnapEnqueue(c, pm::LaunchSnap, sizeof(pm_snap_result), static_cast<const float *>(dev_xyr), n, flags, static_cast<const uint32_t *>(dev_skip_items),
+                       static_cast<uint8_t *>(dev_out), QueryStream(c, hip_stream));
 }
 
 int pm_snap(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_t *skip_items, size_t n_skip, pm_snap_result *out) {
     if (!c) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    int r = SnapCheck(c, xyr, n, flags, skip_items, n_skip, out);
+    const int r = SnapCheck(c, "pm_snap", PM_HIT_SKIP_TRANSPARENT | kSnapKinds, kSnapKinds, xyr, n, flags, skip_items, n_skip, out);
     if (r != PM_OK || n == 0) return r;
-    const size_t batch = std::min(n, kRectBatch);
-    const size_t skip_bytes = skip_items ? static_cast<size_t>(c->n_items) * 4 : 0;
-    PM_TRY(RectStaging(c, batch * 44 + skip_bytes));   // {records, queries, skip words}
-    uint8_t *d_out = c->d_rect;
-    float *d_xyr = reinterpret_cast<float *>(c->d_rect + batch * 32);
-    uint32_t *d_skip = skip_items ? reinterpret_cast<uint32_t *>(c->d_rect + batch * 44) : nullptr;
-    if (skip_bytes) PM_TRY(hipMemcpyAsync(d_skip, skip_items, skip_bytes, hipMemcpyHostToDevice, c->stream));
-    for (size_t at = 0; at < n; at += batch) {
-        const size_t m = std::min(batch, n - at);
-        PM_TRY(hipMemcpyAsync(d_xyr, xyr + 3 * at, m * 12, hipMemcpyHostToDevice, c->stream));
-        r = SnapEnqueue(c, d_xyr, m, flags, d_skip, d_out, c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(out + at, d_out, m * 32, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    return PM_OK;
+    return SnapToHost(c, pm::LaunchSnap, sizeof(*out), xyr, n, flags, skip_items, out);
 }
-
-// ---- snapping to intersections (pm_cross_kernel, pm_snap_cross.h; decision D23) ---------------------------------------------------
-namespace {
-static_assert(sizeof(pm_snap_cross_result) == 48 && offsetof(pm_snap_cross_result, item) == 0 && offsetof(pm_snap_cross_result, kind) == 4 &&
-                  offsetof(pm_snap_cross_result, index) == 8 && offsetof(pm_snap_cross_result, t) == 12 && offsetof(pm_snap_cross_result, x) == 16 &&
-                  offsetof(pm_snap_cross_result, y) == 20 && offsetof(pm_snap_cross_result, d2) == 24 && offsetof(pm_snap_cross_result, item2) == 32 &&
-                  offsetof(pm_snap_cross_result, index2) == 36 && offsetof(pm_snap_cross_result, u) == 40 && offsetof(pm_snap_cross_result, n_near) == 44,
-              "the record pm_cross_kernel writes");
-static_assert(PM_SNAP_MAX_NEAR_EDGES == pm::kCrossMaxNear && PM_SNAP_KIND_INTERSECTION == pm::kSnapKindIntersection && PM_SNAP_KIND_TOO_MANY == pm::kSnapKindTooMany,
-              "pm_snap_cross.h's constants are the header's");
-
-// Everything pm_snap_intersections / pm_snap_intersections_device refuse, before anything is enqueued
-int CrossCheck(pm_ctx *c, const void *xyr, size_t n, uint32_t flags, const void *skip_items, size_t n_skip, const void *out) {
-    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT)) {
-        SetError("pm_snap_intersections: unknown flag bits");
-        return PM_ERR_INVALID;
-    }
-    if (!c->d_scene || c->scene_bytes < 8) {
-        SetError("no scene resident (pm_upload_scene / pm_flatten_and_encode first)");
-        return PM_ERR_INVALID;
-    }
-    if (skip_items ? n_skip < c->n_items : n_skip != 0) {
-        SetError("pm_snap_intersections: skip_items holds one word per item, or is NULL with n_skip == 0");
-        return PM_ERR_INVALID;
-    }
-    if (n != 0 && (!xyr || !out)) {
-        SetError("pm_snap_intersections: a NULL pointer with n != 0");
-        return PM_ERR_INVALID;
-    }
-    return PM_OK;
-}
-
-// SnapEnqueue's ordering (ev_scene before, ev_hit behind), pm_cross_kernel in between
-int CrossEnqueue(pm_ctx *c, const float *d_xyr, size_t n, uint32_t flags, const uint32_t *d_skip, uint8_t *d_out, hipStream_t q) {
-    int r = RectOrderBefore(c, q);
-    if (r != PM_OK) return r;
-    pm::CrossParams p{};
-    p.H = RectParams(c, flags).H;
-    p.skip_items = d_skip;
-    for (size_t at = 0; at < n; at += kHitLaunchMax) {
-        p.xyr = d_xyr + 3 * at;
-        p.out = d_out + 48 * at;
-        p.H.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
-        pm::LaunchCross(p, static_cast<uint32_t>(c->n_cus), q);
-    }
-    return RectOrderBehind(c, q);
-}
-}  // namespace
 
 int pm_snap_intersections_device(pm_ctx *c, const void *dev_xyr, size_t n, uint32_t flags, const void *dev_skip_items, size_t n_skip, void *dev_out,
                                  void *hip_stream) {
     if (!c) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    const int r = CrossCheck(c, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
+    const int r = SnapCheck(c, "pm_snap_intersections", PM_HIT_SKIP_TRANSPARENT, 0u, dev_xyr, n, flags, dev_skip_items, n_skip, dev_out);
     if (r != PM_OK || n == 0) return r;
-    return CrossEnqueue(c, static_cast<const float *>(dev_xyr), n, flags, static_cast<const uint32_t *>(dev_skip_items), static_cast<uint8_t *>(dev_out),
-                        hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return SnapEnqueue(c, pm::LaunchCross, sizeof(pm_snap_cross_result), static_cast<const float *>(dev_xyr), n, flags,
+                       static_cast<const uint32_t *>(dev_skip_items), static_cast<uint8_t *>(dev_out), QueryStream(c, hip_stream));
 }
 
 int pm_snap_intersections(pm_ctx *c, const float *xyr, size_t n, uint32_t flags, const uint32_t *skip_items, size_t n_skip, pm_snap_cross_result *out) {
     if (!c) return PM_ERR_INVALID;
     PM_TRY(hipSetDevice(c->device));
-    int r = CrossCheck(c, xyr, n, flags, skip_items, n_skip, out);
+    const int r = SnapCheck(c, "pm_snap_intersections", PM_HIT_SKIP_TRANSPARENT, 0u, xyr, n, flags, skip_items, n_skip, out);
     if (r != PM_OK || n == 0) return r;
-    const size_t batch = std::min(n, kRectBatch);
-    const size_t skip_bytes = skip_items ? static_cast<size_t>(c->n_items) * 4 : 0;
-    PM_TRY(RectStaging(c, batch * 60 + skip_bytes));   // {records, queries, skip words}
-    uint8_t *d_out = c->d_rect;
-    float *d_xyr = reinterpret_cast<float *>(c->d_rect + batch * 48);
-    uint32_t *d_skip = skip_items ? reinterpret_cast<uint32_t *>(c->d_rect + batch * 60) : nullptr;
-    if (skip_bytes) PM_TRY(hipMemcpyAsync(d_skip, skip_items, skip_bytes, hipMemcpyHostToDevice, c->stream));
-    for (size_t at = 0; at < n; at += batch) {
-        const size_t m = std::min(batch, n - at);
-        PM_TRY(hipMemcpyAsync(d_xyr, xyr + 3 * at, m * 12, hipMemcpyHostToDevice, c->stream));
-        r = CrossEnqueue(c, d_xyr, m, flags, d_skip, d_out, c->stream);
-        if (r != PM_OK) return r;
-        PM_TRY(hipMemcpyAsync(out + at, d_out, m * 48, hipMemcpyDeviceToHost, c->stream));
-        PM_TRY(hipStreamSynchronize(c->stream));
-    }
-    return PM_OK;
+    return SnapToHost(c, pm::LaunchCross, sizeof(*out), xyr, n, flags, skip_items, out);
 }
 
 // ---- bounds (pm_item_bounds_kernel, pm_union_bounds_kernel, pm_bounds.h; decision D22) ---------------------------------------------
@@ -3476,30 +3386,29 @@ int UnionBoundsCheck(pm_ctx *c, uint32_t flags, const void *item_words, size_t n
     return PM_OK;
 }
 
-// HitRectsEnqueue's ordering (ev_scene before, ev_hit behind), the launches in between
 int ItemBoundsEnqueue(pm_ctx *c, uint32_t flags, uint8_t *d_out, hipStream_t q) {
-    int r = RectOrderBefore(c, q);
+    int r = QueryOrderBefore(c, q);
     if (r != PM_OK) return r;
     pm::BoundsParams p{};
-    p.H = RectParams(c, flags).H;
+    p.V = QueryView(c, flags);
     p.out = d_out;
     pm::LaunchItemBounds(p, static_cast<uint32_t>(c->n_cus), q);
-    return RectOrderBehind(c, q);
+    return QueryOrderBehind(c, q);
 }
 
 int UnionBoundsEnqueue(pm_ctx *c, uint32_t flags, const uint32_t *d_words, uint32_t word_mask, const uint32_t *d_labels, uint32_t n_labels, uint8_t *d_out,
                        hipStream_t q) {
-    int r = RectOrderBefore(c, q);
+    int r = QueryOrderBefore(c, q);
     if (r != PM_OK) return r;
     pm::BoundsParams p{};
-    p.H = RectParams(c, flags).H;
+    p.V = QueryView(c, flags);
     p.item_words = d_words;
     p.word_mask = word_mask;
     p.label_of_item = d_labels;
     p.n_labels = n_labels;
     p.out = d_out;
     pm::LaunchUnionBounds(p, static_cast<uint32_t>(c->n_cus), q);
-    return RectOrderBehind(c, q);
+    return QueryOrderBehind(c, q);
 }
 }  // namespace
 
@@ -3514,7 +3423,7 @@ int pm_item_bounds_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap, 
         SetError("pm_item_bounds_device: dev_out is NULL or not 8-byte aligned");
         return PM_ERR_INVALID;
     }
-    return ItemBoundsEnqueue(c, flags, static_cast<uint8_t *>(dev_out), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+    return ItemBoundsEnqueue(c, flags, static_cast<uint8_t *>(dev_out), QueryStream(c, hip_stream));
 }
 
 int pm_item_bounds(pm_ctx *c, uint32_t flags, pm_bounds *out, size_t cap, uint32_t *n_items) {
@@ -3530,10 +3439,10 @@ int pm_item_bounds(pm_ctx *c, uint32_t flags, pm_bounds *out, size_t cap, uint32
         SetError("pm_item_bounds: out is NULL");
         return PM_ERR_INVALID;
     }
-    PM_TRY(RectStaging(c, n * sizeof(pm_bounds)));
-    r = ItemBoundsEnqueue(c, flags, c->d_rect, c->stream);
+    PM_TRY(QueryStaging(c, n * sizeof(pm_bounds)));
+    r = ItemBoundsEnqueue(c, flags, c->d_stage, c->stream);
     if (r != PM_OK) return r;
-    PM_TRY(hipMemcpyAsync(out, c->d_rect, n * sizeof(pm_bounds), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipMemcpyAsync(out, c->d_stage, n * sizeof(pm_bounds), hipMemcpyDeviceToHost, c->stream));
     PM_TRY(hipStreamSynchronize(c->stream));
     return PM_OK;
 }
@@ -3545,7 +3454,7 @@ int pm_union_bounds_device(pm_ctx *c, uint32_t flags, const void *dev_item_words
     const int r = UnionBoundsCheck(c, flags, dev_item_words, n_words, word_mask, dev_label_of_item, n_label_words, n_labels, dev_out);
     if (r != PM_OK) return r;
     return UnionBoundsEnqueue(c, flags, static_cast<const uint32_t *>(dev_item_words), word_mask, static_cast<const uint32_t *>(dev_label_of_item), n_labels,
-                              static_cast<uint8_t *>(dev_out), hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream);
+                              static_cast<uint8_t *>(dev_out), QueryStream(c, hip_stream));
 }
 
 int pm_union_bounds(pm_ctx *c, uint32_t flags, const uint32_t *item_words, size_t n_words, uint32_t word_mask, const uint32_t *label_of_item,
@@ -3556,10 +3465,10 @@ int pm_union_bounds(pm_ctx *c, uint32_t flags, const uint32_t *item_words, size_
     if (r != PM_OK) return r;
     // {records, words, labels}
     const size_t n = c->n_items, out_bytes = static_cast<size_t>(n_labels) * sizeof(pm_label_bounds);
-    PM_TRY(RectStaging(c, out_bytes + (item_words ? n * 4 : 0) + (label_of_item ? n * 4 : 0)));
-    uint8_t *d_out = c->d_rect;
-    uint32_t *d_words = item_words ? reinterpret_cast<uint32_t *>(c->d_rect + out_bytes) : nullptr;
-    uint32_t *d_labels = label_of_item ? reinterpret_cast<uint32_t *>(c->d_rect + out_bytes + (item_words ? n * 4 : 0)) : nullptr;
+    PM_TRY(QueryStaging(c, out_bytes + (item_words ? n * 4 : 0) + (label_of_item ? n * 4 : 0)));
+    uint8_t *d_out = c->d_stage;
+    uint32_t *d_words = item_words ? reinterpret_cast<uint32_t *>(c->d_stage + out_bytes) : nullptr;
+    uint32_t *d_labels = label_of_item ? reinterpret_cast<uint32_t *>(c->d_stage + out_bytes + (item_words ? n * 4 : 0)) : nullptr;
     if (d_words && n) PM_TRY(hipMemcpyAsync(d_words, item_words, n * 4, hipMemcpyHostToDevice, c->stream));
     if (d_labels && n) PM_TRY(hipMemcpyAsync(d_labels, label_of_item, n * 4, hipMemcpyHostToDevice, c->stream));
     r = UnionBoundsEnqueue(c, flags, d_words, word_mask, d_labels, n_labels, d_out, c->stream);

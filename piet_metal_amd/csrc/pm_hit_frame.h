@@ -1,7 +1,8 @@
 // pm_hit_frame_kernel: the item map -- for every pixel of a rectangle the LAST-painted item of the resident scene that contains
 // the pixel's centre (and, if asked, how many do).  Decision D18: it is D13 (pm_hit_test.h) evaluated at (px + 0.5, py + 0.5) and
-// nothing else, so every word equals what pm_hit_kernel answers for that point.  Not on the frame path; included by pm_context.hip
-// after pm_hit_test.h, whose predicates (HitWinding, HitStroke, HitCircle) and constants it uses as they are.
+// nothing else, so every word equals what pm_hit_kernel answers for that point.  Not on the frame path; included by pm_context.hip.
+// D13's predicates (HitWinding, HitStroke, HitCircle), the item head and the constants are pm_query_common.h's, as they are; the walk
+// is the tile's own.
 //
 // One WORKGROUP of 256 threads owns a 16 x 16 tile of the rectangle (tiles are aligned to the rectangle's origin), thread t the
 // pixel (t & 15, t >> 4).  What pm_hit_kernel does per query -- walk the items, test the chunk boxes, stream the segments -- the tile
@@ -33,23 +34,18 @@
 // evaluate are a superset of pm_hit_kernel's, and D13 gives every segment outside that set a contribution of 0.
 #pragma once
 
-#include "pm_hit_test.h"
+#include "pm_query_common.h"
 
 namespace pm {
 
 // One launch of pm_hit_frame_kernel: the w x h pixels from (x0, y0) against the resident scene and its index.
 struct HitFrameParams {
-    const uint8_t *scene;
-    uint32_t n_items, items_ix, bbox_ix;  // the drawn group, as in HitParams
-    const uint32_t *chunk_base;
-    const float4 *chunk_bbox;
-    const float4 *sup_bbox;
+    SceneView V;
     uint32_t *top_item;   // [h][stride], words beyond w in a row are not written
     uint32_t *n_hit;      // the same (nullptr: not asked for -- a pixel is finished at its first hit)
     size_t stride;        // in 32-bit elements
     uint32_t x0, y0, w, h;   // x0 + w <= 65 536, y0 + h <= 65 536: every centre is exact in f32
     uint32_t tiles_x, n_tiles;
-    uint32_t flags;       // PM_HIT_*
 };
 
 namespace {
@@ -94,7 +90,7 @@ __device__ __forceinline__ bool FramePolyBoxOwn(float4 bb, double hw, const Fram
 // the union of eight consecutive entries of the GLOBAL chunk table: the neighbouring items' chunks only make it larger, and
 // the chunks outside [cb0, cb1) are not this item's).
 template <typename Pass, typename Work>
-__device__ __forceinline__ void ForTileChunks(const HitFrameParams &P, uint32_t cb0, uint32_t cb1, uint32_t t, uint32_t *s_part, uint32_t *s_sup,
+__device__ __forceinline__ void ForTileChunks(const SceneView &V, uint32_t cb0, uint32_t cb1, uint32_t t, uint32_t *s_part, uint32_t *s_sup,
                                               uint32_t *s_chunk, Pass &&pass, Work &&work) {
     auto round = [&](bool mine, uint32_t c) {   // one round: compact the passing chunk ids, then everyone works them off
         uint32_t n = 0;
@@ -106,13 +102,13 @@ __device__ __forceinline__ void ForTileChunks(const HitFrameParams &P, uint32_t 
     };
     if (cb1 - cb0 <= kFrameChunks) {
         const uint32_t c = cb0 + t;
-        round(c < cb1 && pass(P.chunk_bbox[c < cb1 ? c : cb0]), c);
+        round(c < cb1 && pass(V.chunk_bbox[c < cb1 ? c : cb0]), c);
         return;
     }
     const uint32_t g1 = (cb1 - 1u) / kSuperChunks + 1u;
     for (uint32_t gb = cb0 / kSuperChunks; gb < g1; gb += kFrameChunks) {
         const uint32_t g = gb + t;
-        const bool keep = g < g1 && pass(P.sup_bbox[g < g1 ? g : gb]);
+        const bool keep = g < g1 && pass(V.sup_bbox[g < g1 ? g : gb]);
         uint32_t ns = 0;
         const uint32_t r = BlockRank<kFrameWaves>(keep, s_part, &ns);
         if (keep) s_sup[r] = g;
@@ -122,7 +118,7 @@ __device__ __forceinline__ void ForTileChunks(const HitFrameParams &P, uint32_t 
             const uint32_t at = sb + t / kSuperChunks;
             const uint32_t c = at < ns ? s_sup[at] * kSuperChunks + (t % kSuperChunks) : cb1;
             const bool in = c >= cb0 && c < cb1;
-            round(in && pass(P.chunk_bbox[in ? c : cb0]), c);
+            round(in && pass(V.chunk_bbox[in ? c : cb0]), c);
         }
     }
 }
@@ -135,10 +131,11 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
     __shared__ uint32_t s_chunk[kFrameChunks];  // a round's surviving chunks
     __shared__ uint32_t s_part[kFrameWaves];    // BlockRank's
     __shared__ uint32_t s_live[2][kFrameWaves]; // waves with a live pixel, two generations (one barrier per look)
+    const SceneView &V = P.V;
     const uint32_t t = threadIdx.x;
     const uint32_t wave = t >> 6;
     const bool counts = P.n_hit != nullptr;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
     for (uint32_t tile = blockIdx.x; tile < P.n_tiles; tile += gridDim.x) {
         const uint32_t ox = (tile % P.tiles_x) * kFrameTile, oy = (tile / P.tiles_x) * kFrameTile;   // in the rectangle
         const uint32_t ix = ox + (t % kFrameTile), iy = oy + (t / kFrameTile);
@@ -153,15 +150,13 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
         T.live = inside;
         uint32_t top = kHitNone, cnt = 0, looks = 0;
         bool tile_done = false;
-        for (uint32_t hi = P.n_items; hi != 0u && !tile_done; hi = hi > kFrameItems ? hi - kFrameItems : 0u) {
+        for (uint32_t hi = V.n_items; hi != 0u && !tile_done; hi = hi > kFrameItems ? hi - kFrameItems : 0u) {
             // thread 0 looks at the topmost item of the step
             bool keep = false;
             const uint32_t mine = hi - 1u - t;
             if (t < hi) {
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(mine) * kItemSize;
-                const uint32_t tag = LoadU32(it) & 0xffffu;
-                const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(mine) * sizeof(ShortBbox));
-                const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
+                const ItemHead h = LoadItemHead(V, mine);
+                const uint32_t tag = h.tag, x0 = h.x0, y0 = h.y0, x1 = h.x1, y1 = h.y1;
                 if (tag == kItemCircle) {  // the box IS the shape: no edge of it is "saturated"
                     keep = !(T.ymax < static_cast<double>(y0) || T.ymin > static_cast<double>(y1) || T.xmax < static_cast<double>(x0) ||
                              T.xmin > static_cast<double>(x1));
@@ -170,11 +165,11 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
                     const bool above = y0 != 0u && T.ymax < static_cast<double>(y0), below = y1 != 0xffffu && T.ymin > static_cast<double>(y1);
                     const bool left = x0 != 0u && T.xmax < static_cast<double>(x0), right = x1 != 0xffffu && T.xmin > static_cast<double>(x1);
                     if (tag == kItemLine) {
-                        keep = !(skip && (LoadU32(it + 8) >> 24) == 0u);
+                        keep = !(skip && ItemTransparent(h));
                     } else if (tag == kItemFill) {
-                        keep = !(above || below || right) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
+                        keep = !(above || below || right) && !(skip && ItemTransparent(h));
                     } else if (tag == kItemPoly) {
-                        keep = !(above || below || left || right) && !(skip && (LoadU32(it + 4) >> 24) == 0u);
+                        keep = !(above || below || left || right) && !(skip && ItemTransparent(h));
                     }
                 }
             }
@@ -198,15 +193,12 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
                     }
                 }
                 const uint32_t i = Uniform(s_cand[k]);
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                const uint32_t w0 = LoadU32(it);
-                const uint32_t tag = w0 & 0xffffu;
+                const ItemHead h = LoadItemHead(V, i);
+                const uint8_t *it = h.it;
+                const uint32_t tag = h.tag;
                 bool hit = false;
                 if (tag == kItemCircle) {
-                    if (T.live) {
-                        const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-                        hit = HitCircle(bb.x & 0xffffu, bb.x >> 16, bb.y & 0xffffu, bb.y >> 16, (w0 & kCircleEllipse) != 0, T.x, T.y);
-                    }
+                    if (T.live) hit = HitCircle(h.x0, h.y0, h.x1, h.y1, (h.w0 & kCircleEllipse) != 0, T.x, T.y);
                 } else if (tag == kItemLine) {
                     if (T.live) {
                         const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 12)));
@@ -214,14 +206,14 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
                     }
                 } else if (tag == kItemFill) {
                     const uint32_t flags = LoadU32(it + 4), npt = LoadU32(it + 12);
-                    const uint8_t *pts = P.scene + LoadU32(it + 16);
+                    const uint8_t *pts = V.scene + LoadU32(it + 16);
                     const bool compound = (flags & kFillCompound) != 0;
-                    const uint32_t cb0 = P.chunk_base[i], cb1 = P.chunk_base[i + 1];
+                    const uint32_t cb0 = V.chunk_base[i], cb1 = V.chunk_base[i + 1];
                     int wsum = 0;
                     ForTileChunks(
-                        P, cb0, cb1, t, s_part, s_sup, s_chunk, [&](float4 bb) { return FrameFillBoxTile(bb, T); },
+                        V, cb0, cb1, t, s_part, s_sup, s_chunk, [&](float4 bb) { return FrameFillBoxTile(bb, T); },
                         [&](uint32_t c) {
-                            if (!(T.live && FrameFillBoxOwn(P.chunk_bbox[c], T))) return;
+                            if (!(T.live && FrameFillBoxOwn(V.chunk_bbox[c], T))) return;
                             const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, FillSegs(npt));
                             for (uint32_t s = k0; s < k1; ++s) {
                                 float2 a, b;
@@ -231,18 +223,18 @@ __global__ __launch_bounds__(kFrameThreads) void pm_hit_frame_kernel(HitFramePar
                     hit = (flags & kFillEvenOdd) ? (wsum & 1) != 0 : wsum != 0;
                 } else if (tag == kItemPoly) {
                     const uint32_t npt = LoadU32(it + 12);
-                    const uint8_t *pts = P.scene + LoadU32(it + 16);
+                    const uint8_t *pts = V.scene + LoadU32(it + 16);
                     const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 8)));
                     const double hw2 = hw * hw;
                     if (npt == 1u) {  // one degenerate segment (the scene index has no chunk for it)
                         const float2 a = LoadF2(pts);
                         hit = T.live && HitStroke(a, a, T.x, T.y, hw2);
                     } else if (npt != 0u) {
-                        const uint32_t cb0 = P.chunk_base[i], cb1 = P.chunk_base[i + 1];
+                        const uint32_t cb0 = V.chunk_base[i], cb1 = V.chunk_base[i + 1];
                         ForTileChunks(
-                            P, cb0, cb1, t, s_part, s_sup, s_chunk, [&](float4 bb) { return FramePolyBoxTile(bb, hw, T); },
+                            V, cb0, cb1, t, s_part, s_sup, s_chunk, [&](float4 bb) { return FramePolyBoxTile(bb, hw, T); },
                             [&](uint32_t c) {
-                                if (hit || !(T.live && FramePolyBoxOwn(P.chunk_bbox[c], hw, T))) return;
+                                if (hit || !(T.live && FramePolyBoxOwn(V.chunk_bbox[c], hw, T))) return;
                                 const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, PolySegs(npt));
                                 float2 a = LoadF2(pts + static_cast<size_t>(k0) * 8);
                                 for (uint32_t s = k0; s < k1; ++s) {

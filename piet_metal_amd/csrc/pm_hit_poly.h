@@ -1,8 +1,8 @@
 // pm_select_polygon_kernel: polygon queries -- which items a query polygon K of 3 .. 4096 vertices TOUCHES and which it ENCLOSES,
 // under the non-zero or the even-odd rule: lasso selection, and a marquee dragged in a rotated view.  Not on the frame path: like
 // pm_select_rect_kernel it reads the scene and the scene index, nothing a frame writes.  Included by pm_context.hip after
-// pm_hit_rect.h, whose predicates (HitWinding, HitStroke), chunk walk (ForItemChunks), segment reading (FillSegmentEnds) and
-// constants are used as they are.
+// pm_hit_rect.h (RectQ, RectOverlaps); D13's predicates (HitWinding, HitStroke), the chunk walk (ForItemChunks), the item head
+// and the constants are pm_query_common.h's, as they are.
 //
 // What "touches" and "encloses" mean is decision D20: binary64 arithmetic on the scene's f32 / u16 values and the
 // polygon's f32 values, one rounding per written operation, in the written order (-ffp-contract=off) -- tests/np_poly.py states
@@ -48,7 +48,7 @@ namespace pm {
 
 // One launch of pm_select_polygon_kernel
 struct HitPolyParams {
-    HitParams H;            // the scene, its index and the PM_HIT_* flags
+    SceneView V;
     const float *verts;     // [2 m] K's vertices, device memory
     const float *boxes;     // [4 ceil(m / kPolyGroup)] {min x, min y, max x, max y} of the ends of edges g kPolyGroup .. (group g)
     uint32_t m;             // 3 .. kPolyMaxVertices
@@ -221,18 +221,18 @@ __device__ __forceinline__ bool PolyPoints(const PolyQ &K, const uint8_t *pts, u
 }
 
 // Fill item `item`: PM_SEL_* of it (wave-uniform arguments and result)
-__device__ __forceinline__ uint32_t PolyFill(const HitParams &P, uint32_t item, const uint8_t *it, const PolyQ &K, uint32_t lane) {
+__device__ __forceinline__ uint32_t PolyFill(const SceneView &V, uint32_t item, const uint8_t *it, const PolyQ &K, uint32_t lane) {
     const uint32_t flags = LoadU32(it + 4), npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const bool compound = (flags & kFillCompound) != 0;
     bool any_in, all_in;
     if (!PolyPoints(K, pts, npt, compound, lane, any_in, all_in)) return 0u;
     if (any_in && !all_in) return kSelTouches;
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     int w = 0;
     bool reach = false, any = false;
     ForItemChunks(
-        P, cb0, cb1, lane,
+        V, cb0, cb1, lane,
         [&](float4 bb) {
             const bool winds = static_cast<double>(bb.y) <= K.v0y && K.v0y < static_cast<double>(bb.w) && static_cast<double>(bb.z) >= K.v0x;
             return winds || RectOverlaps(K.box, bb);
@@ -260,9 +260,9 @@ __device__ __forceinline__ uint32_t PolyFill(const HitParams &P, uint32_t item, 
 }
 
 // Polyline item `item`: PM_SEL_* of it
-__device__ __forceinline__ uint32_t PolyPoly(const HitParams &P, uint32_t item, const uint8_t *it, const PolyQ &K, uint32_t lane) {
+__device__ __forceinline__ uint32_t PolyPoly(const SceneView &V, uint32_t item, const uint8_t *it, const PolyQ &K, uint32_t lane) {
     const uint32_t npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 8)));
     const double hw2 = hw * hw, wide = fabs(hw);
     if (npt == 0u || hw != hw) return 0u;
@@ -274,10 +274,10 @@ __device__ __forceinline__ uint32_t PolyPoly(const HitParams &P, uint32_t item, 
         const float2 a = LoadF2(pts);
         any = PolyReach(K, a, a, true, hw2, wide);
     } else {
-        const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+        const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
         const double kmax = PolyMaxAbs(K.box);
         ForItemChunks(
-            P, cb0, cb1, lane,
+            V, cb0, cb1, lane,
             [&](float4 bb) {
                 const double far = wide + fmax(kmax, PolyMaxAbs(bb)) * kPolyPad;
                 return !(K.box.x1 < static_cast<double>(bb.x) - far || K.box.x0 > static_cast<double>(bb.z) + far ||
@@ -318,10 +318,9 @@ __device__ __forceinline__ bool PolyCandidate(const PolyQ &K, uint32_t x0, uint3
 }  // namespace
 
 __global__ __launch_bounds__(kHitThreads) void pm_select_polygon_kernel(HitPolyParams Q) {
-    const HitParams &P = Q.H;
+    const SceneView &V = Q.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
     const bool valid = Q.valid != 0u && Q.m >= 3u && Q.m <= kPolyMaxVertices;
     PolyQ K;
     K.v = reinterpret_cast<const uint8_t *>(Q.verts);
@@ -338,49 +337,40 @@ __global__ __launch_bounds__(kHitThreads) void pm_select_polygon_kernel(HitPolyP
         K.v0x = static_cast<double>(v0.x);
         K.v0y = static_cast<double>(v0.y);
     }
-    const uint32_t n_steps = (P.n_items + 63u) / 64u;
-    for (uint32_t step = blockIdx.x * kHitWaves + WaveId(); step < n_steps; step += n_waves) {
+    const uint32_t n_waves = GridWaves(), n_steps = ItemSteps(V.n_items);
+    for (uint32_t step = FirstWaveUnit(); step < n_steps; step += n_waves) {
         // lane 0 looks at the topmost item of the step
-        const uint32_t hi = min(step * 64u + 64u, P.n_items);
+        const uint32_t hi = min(step * 64u + 64u, V.n_items);
         const bool mine = step * 64u + lane < hi;
         const uint32_t i = mine ? hi - 1u - lane : 0u;
         uint32_t word = 0u;
         bool cand = false;
         if (mine && valid) {
-            const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-            const uint32_t w0 = LoadU32(it);
-            const uint32_t tag = w0 & 0xffffu;
-            const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-            const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
-            if (tag == kItemCircle) {
-                word = PolyCircle(K, x0, y0, x1, y1, (w0 & kCircleEllipse) != 0);
-            } else if (tag == kItemLine) {
-                if (!(skip && (LoadU32(it + 8) >> 24) == 0u)) word = PolyLine(K, it);
-            } else if (tag == kItemFill) {
-                cand = PolyCandidate(K, x0, y0, x1, y1, true) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
-            } else if (tag == kItemPoly) {
-                cand = PolyCandidate(K, x0, y0, x1, y1, false) && !(skip && (LoadU32(it + 4) >> 24) == 0u);
+            const ItemHead h = LoadItemHead(V, i);
+            if (h.tag == kItemCircle) {
+                word = PolyCircle(K, h.x0, h.y0, h.x1, h.y1, (h.w0 & kCircleEllipse) != 0);
+            } else if (h.tag == kItemLine) {
+                if (!(skip && ItemTransparent(h))) word = PolyLine(K, h.it);
+            } else if (h.tag == kItemFill) {
+                cand = PolyCandidate(K, h.x0, h.y0, h.x1, h.y1, true) && !(skip && ItemTransparent(h));
+            } else if (h.tag == kItemPoly) {
+                cand = PolyCandidate(K, h.x0, h.y0, h.x1, h.y1, false) && !(skip && ItemTransparent(h));
             }
         }
         uint64_t m = __ballot(cand);
         while (m != 0ull) {   // every candidate is finished: no item's word waits for another's
-            const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-            m &= m - 1ull;
-            const uint32_t c = hi - 1u - l;
-            const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(c) * kItemSize;
-            const uint32_t w = (LoadU32(it) & 0xffffu) == kItemFill ? PolyFill(P, c, it, K, lane) : PolyPoly(P, c, it, K, lane);
+            const uint32_t l = TakeLowestLane(m);
+            const ItemHead h = LoadItemHead(V, hi - 1u - l);
+            const uint32_t w = h.tag == kItemFill ? PolyFill(V, h.item, h.it, K, lane) : PolyPoly(V, h.item, h.it, K, lane);
             if (lane == l) word = w;
         }
         if (mine) Q.item_flags[i] = word;
     }
 }
 
-// grid: a wave per step of 64 items, at most what the chip holds at once (eight workgroups of four waves per CU)
+// grid: a wave per step of 64 items, at most what the chip holds at once
 void LaunchSelectPolygon(const HitPolyParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n_items == 0u) return;
-    const uint32_t n_steps = (p.H.n_items + 63u) / 64u;
-    const uint32_t grid = min((n_steps + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_select_polygon_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
+    LaunchQuery(pm_select_polygon_kernel, p, ItemSteps(p.V.n_items), n_cus, stream);
 }
 
 }  // namespace pm

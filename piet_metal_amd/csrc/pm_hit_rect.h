@@ -1,8 +1,8 @@
 // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries -- does an item's shape have a point in common with a closed
 // axis-aligned rectangle R (it TOUCHES R), and does all of it lie in R (R ENCLOSES it).  Picking with a tolerance is the first
 // question asked of a small square around the cursor, marquee selection is both asked of every item.  Not on the frame path:
-// like pm_hit_kernel they read the scene and the scene index, nothing a frame writes.  Included by pm_context.hip after
-// pm_hit_test.h, whose predicates (HitWinding, HitStroke), chunk walk (ForItemChunks) and constants are used as they are.
+// like pm_hit_kernel they read the scene and the scene index, nothing a frame writes.  Included by pm_context.hip; D13's predicates
+// (HitWinding, HitStroke), the chunk walk (ForItemChunks), the item head and the constants are pm_query_common.h's, as they are.
 //
 // What "touches" and "encloses" mean is decision D19: binary64 arithmetic on the scene's f32 / u16 values and the
 // query's f32 values, one rounding per written operation, in the written order (-ffp-contract=off) -- tests/np_rect.py states
@@ -34,38 +34,39 @@
 //    is not enclosed that is nearly always the first.
 #pragma once
 
-#include "pm_hit_test.h"
+#include "pm_query_common.h"
 
 namespace pm {
 
-// One launch of either kernel.  H: the scene, its index and the flags; pm_hit_rects_kernel also takes its outputs and the
-// number of queries from it (H.top_item, H.n_hit, H.n; H.xy is unused).
+// One launch of pm_hit_rects_kernel: n query rectangles
 struct HitRectParams {
-    HitParams H;
-    const float *rects;     // pm_hit_rects_kernel: [4 n] {x0, y0, x1, y1}
-    uint32_t *item_flags;   // pm_select_rect_kernel: [n_items] PM_SEL_*
-    float rect[4];          // pm_select_rect_kernel: the rectangle
+    SceneView V;
+    const float *rects;     // [4 n] {x0, y0, x1, y1}
+    uint32_t *top_item;     // [n] last-painted item that touches the rectangle, or 0xffffffff
+    uint32_t *n_hit;        // [n] items that touch it (nullptr: not asked for -- the walk ends at the first)
+    uint32_t n;
+};
+
+// One launch of pm_select_rect_kernel: one rectangle against every item
+struct SelectRectParams {
+    SceneView V;
+    uint32_t *item_flags;   // [n_items] PM_SEL_*
+    float rect[4];
 };
 
 namespace {
-
-constexpr uint32_t kSelTouches = 1u;    // PM_SEL_TOUCHES
-constexpr uint32_t kSelEncloses = 2u;   // PM_SEL_ENCLOSES
 
 // The query rectangle in binary64 (wave-uniform)
 struct RectQ {
     double x0, y0, x1, y1;
 };
 
-__device__ __forceinline__ bool RectFiniteBits(uint32_t b) { return (b & 0x7f800000u) != 0x7f800000u; }
-__device__ __forceinline__ bool RectFinite(float2 p) { return RectFiniteBits(__float_as_uint(p.x)) && RectFiniteBits(__float_as_uint(p.y)); }
-
 // D19: a rectangle with a non-finite value, or with x1 < x0 or y1 < y0, touches nothing and encloses nothing
 __device__ __forceinline__ bool RectLoad(const float *r, RectQ &R) {
-    const uint32_t b0 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(r[0]))));
-    const uint32_t b1 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(r[1]))));
-    const uint32_t b2 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(r[2]))));
-    const uint32_t b3 = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(r[3]))));
+    const uint32_t b0 = UniformF32Bits(__float_as_uint(r[0]));
+    const uint32_t b1 = UniformF32Bits(__float_as_uint(r[1]));
+    const uint32_t b2 = UniformF32Bits(__float_as_uint(r[2]));
+    const uint32_t b3 = UniformF32Bits(__float_as_uint(r[3]));
     R.x0 = static_cast<double>(__uint_as_float(b0));
     R.y0 = static_cast<double>(__uint_as_float(b1));
     R.x1 = static_cast<double>(__uint_as_float(b2));
@@ -137,15 +138,15 @@ __device__ __forceinline__ bool RectOverlaps(const RectQ &R, float4 bb) {
 }
 
 // Does Fill item `item` touch R (wave-uniform arguments and result)
-__device__ __forceinline__ bool RectFill(const HitParams &P, uint32_t item, const uint8_t *it, const RectQ &R, uint32_t lane) {
+__device__ __forceinline__ bool RectFill(const SceneView &V, uint32_t item, const uint8_t *it, const RectQ &R, uint32_t lane) {
     const uint32_t flags = LoadU32(it + 4), npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const bool compound = (flags & kFillCompound) != 0;
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     int w = 0;
     bool meets = false, any = false;
     ForItemChunks(
-        P, cb0, cb1, lane,
+        V, cb0, cb1, lane,
         [&](float4 bb) {
             const bool winds = static_cast<double>(bb.y) <= R.y0 && R.y0 < static_cast<double>(bb.w) && static_cast<double>(bb.z) >= R.x0;
             return winds || RectOverlaps(R, bb);
@@ -170,9 +171,9 @@ __device__ __forceinline__ bool RectFill(const HitParams &P, uint32_t item, cons
 }
 
 // Does Polyline item `item` touch R
-__device__ __forceinline__ bool RectPoly(const HitParams &P, uint32_t item, const uint8_t *it, const RectQ &R, uint32_t lane) {
+__device__ __forceinline__ bool RectPoly(const SceneView &V, uint32_t item, const uint8_t *it, const RectQ &R, uint32_t lane) {
     const uint32_t npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 8)));
     const double hw2 = hw * hw, wide = fabs(hw);
     if (npt == 0u || hw != hw) return false;
@@ -180,10 +181,10 @@ __device__ __forceinline__ bool RectPoly(const HitParams &P, uint32_t item, cons
         const float2 a = LoadF2(pts);
         return RectStroke(R, a, a, hw2);
     }
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     bool hit = false, any = false;
     ForItemChunks(
-        P, cb0, cb1, lane,
+        V, cb0, cb1, lane,
         [&](float4 bb) {
             return !(R.x1 < static_cast<double>(bb.x) - wide || R.x0 > static_cast<double>(bb.z) + wide || R.y1 < static_cast<double>(bb.y) - wide ||
                      R.y0 > static_cast<double>(bb.w) + wide);
@@ -234,48 +235,47 @@ __device__ __forceinline__ bool RectCandidate(const RectQ &R, uint32_t x0, uint3
     return !apart || (fill && !corner_out);
 }
 
+// What a lane makes of a Fill's or a Polyline's head for both kernels: a candidate by its box, unless the flags skip it
+__device__ __forceinline__ bool RectCandidate(const RectQ &R, const ItemHead &h, bool fill, bool skip) {
+    return RectCandidate(R, h.x0, h.y0, h.x1, h.y1, fill) && !(skip && ItemTransparent(h));
+}
+
 }  // namespace
 
 __global__ __launch_bounds__(kHitThreads) void pm_hit_rects_kernel(HitRectParams Q) {
-    const HitParams &P = Q.H;
+    const SceneView &V = Q.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const bool counts = P.n_hit != nullptr;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
-    for (uint32_t q = blockIdx.x * kHitWaves + WaveId(); q < P.n; q += n_waves) {
+    const bool counts = Q.n_hit != nullptr;
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
+    const uint32_t n_waves = GridWaves();
+    for (uint32_t q = FirstWaveUnit(); q < Q.n; q += n_waves) {
         RectQ R;
-        bool done = !RectLoad(Q.rects + static_cast<size_t>(q) * 4, R);
+        const bool valid = RectLoad(Q.rects + static_cast<size_t>(q) * 4, R);
+        bool done = !valid;
         uint32_t top = kHitNone, cnt = 0;
-        for (uint32_t hi = P.n_items; hi != 0u && !done; hi = hi > 64u ? hi - 64u : 0u) {
+        for (uint32_t hi = V.n_items; hi != 0u && !done; hi = hi > 64u ? hi - 64u : 0u) {
             // lane 0 looks at the topmost item of the step
             bool direct = false, cand = false;
             if (lane < hi) {
-                const uint32_t i = hi - 1u - lane;
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                const uint32_t w0 = LoadU32(it);
-                const uint32_t tag = w0 & 0xffffu;
-                const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-                const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
-                if (tag == kItemCircle) {
-                    direct = (RectCircle(R, x0, y0, x1, y1, (w0 & kCircleEllipse) != 0) & kSelTouches) != 0u;
-                } else if (tag == kItemLine) {
-                    if (!(skip && (LoadU32(it + 8) >> 24) == 0u)) direct = (RectLine(R, it) & kSelTouches) != 0u;
-                } else if (tag == kItemFill) {
-                    cand = RectCandidate(R, x0, y0, x1, y1, true) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
-                } else if (tag == kItemPoly) {
-                    cand = RectCandidate(R, x0, y0, x1, y1, false) && !(skip && (LoadU32(it + 4) >> 24) == 0u);
+                const ItemHead h = LoadItemHead(V, hi - 1u - lane);
+                if (h.tag == kItemCircle) {
+                    direct = (RectCircle(R, h.x0, h.y0, h.x1, h.y1, (h.w0 & kCircleEllipse) != 0) & kSelTouches) != 0u;
+                } else if (h.tag == kItemLine) {
+                    if (!(skip && ItemTransparent(h))) direct = (RectLine(R, h.it) & kSelTouches) != 0u;
+                } else if (h.tag == kItemFill) {
+                    cand = RectCandidate(R, h, true, skip);
+                } else if (h.tag == kItemPoly) {
+                    cand = RectCandidate(R, h, false, skip);
                 }
             }
             const uint64_t md = __ballot(direct);
             uint64_t m = md | __ballot(cand);
             while (m != 0ull) {
-                const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-                m &= m - 1ull;
+                const uint32_t l = TakeLowestLane(m);
                 bool hit = ((md >> l) & 1ull) != 0ull;
                 if (!hit) {
-                    const uint32_t i = hi - 1u - l;
-                    const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                    hit = (LoadU32(it) & 0xffffu) == kItemFill ? RectFill(P, i, it, R, lane) : RectPoly(P, i, it, R, lane);
+                    const ItemHead h = LoadItemHead(V, hi - 1u - l);
+                    hit = h.tag == kItemFill ? RectFill(V, h.item, h.it, R, lane) : RectPoly(V, h.item, h.it, R, lane);
                 }
                 if (hit) {
                     if (top == kHitNone) top = hi - 1u - l;
@@ -288,58 +288,51 @@ __global__ __launch_bounds__(kHitThreads) void pm_hit_rects_kernel(HitRectParams
             }
         }
         if (lane == 0u) {
-            P.top_item[q] = top;
-            if (counts) P.n_hit[q] = cnt;
+            Q.top_item[q] = top;
+            if (counts) Q.n_hit[q] = cnt;
         }
     }
 }
 
-__global__ __launch_bounds__(kHitThreads) void pm_select_rect_kernel(HitRectParams Q) {
-    const HitParams &P = Q.H;
+__global__ __launch_bounds__(kHitThreads) void pm_select_rect_kernel(SelectRectParams Q) {
+    const SceneView &V = Q.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
     RectQ R;
     const bool valid = RectLoad(Q.rect, R);
-    const uint32_t n_steps = (P.n_items + 63u) / 64u;
-    for (uint32_t step = blockIdx.x * kHitWaves + WaveId(); step < n_steps; step += n_waves) {
+    const uint32_t n_waves = GridWaves(), n_steps = ItemSteps(V.n_items);
+    for (uint32_t step = FirstWaveUnit(); step < n_steps; step += n_waves) {
         // lane 0 looks at the topmost item of the step
-        const uint32_t hi = min(step * 64u + 64u, P.n_items);
+        const uint32_t hi = min(step * 64u + 64u, V.n_items);
         const bool mine = step * 64u + lane < hi;
         const uint32_t i = mine ? hi - 1u - lane : 0u;
         uint32_t word = 0u;
         bool cand = false;
         if (mine && valid) {
-            const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-            const uint32_t w0 = LoadU32(it);
-            const uint32_t tag = w0 & 0xffffu;
-            const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-            const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
-            if (tag == kItemCircle) {
-                word = RectCircle(R, x0, y0, x1, y1, (w0 & kCircleEllipse) != 0);
-            } else if (tag == kItemLine) {
-                if (!(skip && (LoadU32(it + 8) >> 24) == 0u)) word = RectLine(R, it);
-            } else if (tag == kItemFill) {
-                cand = RectCandidate(R, x0, y0, x1, y1, true) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
-            } else if (tag == kItemPoly) {
-                cand = RectCandidate(R, x0, y0, x1, y1, false) && !(skip && (LoadU32(it + 4) >> 24) == 0u);
+            const ItemHead h = LoadItemHead(V, i);
+            if (h.tag == kItemCircle) {
+                word = RectCircle(R, h.x0, h.y0, h.x1, h.y1, (h.w0 & kCircleEllipse) != 0);
+            } else if (h.tag == kItemLine) {
+                if (!(skip && ItemTransparent(h))) word = RectLine(R, h.it);
+            } else if (h.tag == kItemFill) {
+                cand = RectCandidate(R, h, true, skip);
+            } else if (h.tag == kItemPoly) {
+                cand = RectCandidate(R, h, false, skip);
             }
         }
         uint64_t m = __ballot(cand);
         while (m != 0ull) {   // every candidate is finished: no item's word waits for another's
-            const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-            m &= m - 1ull;
-            const uint32_t c = hi - 1u - l;
-            const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(c) * kItemSize;
-            const uint32_t npt = LoadU32(it + 12);
-            const uint8_t *pts = P.scene + LoadU32(it + 16);
+            const uint32_t l = TakeLowestLane(m);
+            const ItemHead h = LoadItemHead(V, hi - 1u - l);
+            const uint32_t npt = LoadU32(h.it + 12);
+            const uint8_t *pts = V.scene + LoadU32(h.it + 16);
             bool touches, encloses;
-            if ((LoadU32(it) & 0xffffu) == kItemFill) {
-                touches = RectFill(P, c, it, R, lane);
-                encloses = RectEnclosesPoints(pts, npt, (LoadU32(it + 4) & kFillCompound) != 0, 0.0, R, lane);
+            if (h.tag == kItemFill) {
+                touches = RectFill(V, h.item, h.it, R, lane);
+                encloses = RectEnclosesPoints(pts, npt, (LoadU32(h.it + 4) & kFillCompound) != 0, 0.0, R, lane);
             } else {
-                const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(it + 8)));
-                touches = RectPoly(P, c, it, R, lane);
+                const double hw = 0.5 * static_cast<double>(__uint_as_float(LoadU32(h.it + 8)));
+                touches = RectPoly(V, h.item, h.it, R, lane);
                 encloses = RectEnclosesPoints(pts, npt, false, hw, R, lane);
             }
             if (lane == l) word = (touches ? kSelTouches : 0u) | (encloses ? kSelEncloses : 0u);
@@ -348,19 +341,11 @@ __global__ __launch_bounds__(kHitThreads) void pm_select_rect_kernel(HitRectPara
     }
 }
 
-// grid: what the chip holds at once (eight workgroups of four waves per CU), or a wave per query if that is less
-void LaunchHitRects(const HitRectParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n == 0u) return;
-    const uint32_t grid = min((p.H.n + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_hit_rects_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
-}
+void LaunchHitRects(const HitRectParams &p, uint32_t n_cus, hipStream_t stream) { LaunchQuery(pm_hit_rects_kernel, p, p.n, n_cus, stream); }
 
 // ... or a wave per step of 64 items
-void LaunchSelectRect(const HitRectParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n_items == 0u) return;
-    const uint32_t n_steps = (p.H.n_items + 63u) / 64u;
-    const uint32_t grid = min((n_steps + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_select_rect_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
+void LaunchSelectRect(const SelectRectParams &p, uint32_t n_cus, hipStream_t stream) {
+    LaunchQuery(pm_select_rect_kernel, p, ItemSteps(p.V.n_items), n_cus, stream);
 }
 
 }  // namespace pm

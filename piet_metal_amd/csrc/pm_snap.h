@@ -1,7 +1,7 @@
 // pm_snap_kernel: snapping -- for every query {x, y, r} the nearest vertex and the nearest point of an edge of the resident scene
 // within r of (x, y): which item, which vertex or which point of which segment, and how far.  Not on the frame path: like the
-// other query kernels it reads the scene and the scene index, nothing a frame writes.  Included by pm_context.hip after
-// pm_hit_rect.h; the chunk walk (ForItemChunks), FillSegmentEnds and the constants are used as they are.
+// other query kernels it reads the scene and the scene index, nothing a frame writes.  Included by pm_context.hip; the item
+// head, the chunk walk (ForItemChunks) and the constants are pm_query_common.h's, as they are.
 //
 // What an item offers, how far a candidate is and which one wins is decision D21: binary64 arithmetic on the
 // scene's f32 / u16 values and the query's f32 values, one rounding per written operation, in the written order
@@ -40,16 +40,17 @@
 // The running best is NOT used to cull: r alone bounds the search.
 #pragma once
 
-#include "pm_hit_rect.h"
+#include "pm_query_common.h"
 
 namespace pm {
 
-// One launch of pm_snap_kernel.  H: the scene, its index, the flags and the number of queries (H.xy, H.top_item, H.n_hit unused).
+// One launch of pm_snap_kernel
 struct SnapParams {
-    HitParams H;
+    SceneView V;                 // flags: PM_HIT_SKIP_TRANSPARENT and PM_SNAP_VERTICES / PM_SNAP_EDGES
     const float *xyr;            // [3 n] {x, y, r}
     const uint32_t *skip_items;  // [n_items] a non-zero word takes the item out of the search (nullptr: none)
     uint8_t *out;                // [32 n] pm_snap_result
+    uint32_t n;
 };
 
 namespace {
@@ -64,6 +65,18 @@ struct SnapQ {
     double x, y, r2;
     bool vertices, edges;
 };
+
+// D21 (and D23): query {x, y, r} at in[0 .. 2]; a non-finite value, or r < 0, snaps to nothing
+__device__ __forceinline__ bool SnapLoad(const float *in, SnapQ &Q) {
+    const uint32_t xb = UniformF32Bits(__float_as_uint(in[0]));
+    const uint32_t yb = UniformF32Bits(__float_as_uint(in[1]));
+    const uint32_t rb = UniformF32Bits(__float_as_uint(in[2]));
+    const double r = static_cast<double>(__uint_as_float(rb));
+    Q.x = static_cast<double>(__uint_as_float(xb));
+    Q.y = static_cast<double>(__uint_as_float(yb));
+    Q.r2 = r * r;
+    return RectFiniteBits(xb) && RectFiniteBits(yb) && RectFiniteBits(rb) && !(r < 0.0);
+}
 
 // A lane's best candidate of one kind.  d2 = all ones: none yet (no qualifying d2 has that pattern: it is <= r * r, finite)
 struct SnapBest {
@@ -124,13 +137,13 @@ __device__ __forceinline__ bool SnapPass(const SnapQ &Q, float4 bb) {
 }
 
 // Fill item `item` (wave-uniform arguments): every entry k is met once, as the start of its segment
-__device__ __forceinline__ void SnapFill(const HitParams &P, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, SnapBest &bv, SnapBest &be) {
+__device__ __forceinline__ void SnapFill(const SceneView &V, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, SnapBest &bv, SnapBest &be) {
     const uint32_t flags = LoadU32(it + 4), npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const bool compound = (flags & kFillCompound) != 0;
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     ForItemChunks(
-        P, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
+        V, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
         [&](uint32_t c) {
             const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, FillSegs(npt));
             for (uint32_t k = k0; k < k1; ++k) {
@@ -144,9 +157,9 @@ __device__ __forceinline__ void SnapFill(const HitParams &P, uint32_t item, cons
 }
 
 // Polyline item `item`: point k is met as the start of segment k, the last point as the end of the last segment
-__device__ __forceinline__ void SnapPoly(const HitParams &P, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, SnapBest &bv, SnapBest &be) {
+__device__ __forceinline__ void SnapPoly(const SceneView &V, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, SnapBest &bv, SnapBest &be) {
     const uint32_t npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     if (npt == 0u) return;
     if (npt == 1u) {  // one vertex and one degenerate segment (the scene index has no chunk for it)
         if (lane == 0u) {
@@ -156,9 +169,9 @@ __device__ __forceinline__ void SnapPoly(const HitParams &P, uint32_t item, cons
         }
         return;
     }
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     ForItemChunks(
-        P, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
+        V, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
         [&](uint32_t c) {
             const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, PolySegs(npt));
             float2 a = LoadF2(pts + static_cast<size_t>(k0) * 8);
@@ -175,10 +188,10 @@ __device__ __forceinline__ void SnapPoly(const HitParams &P, uint32_t item, cons
         [] { return false; });
 }
 
-// Is the ShortBbox {x0, y0, x1, y1} a reason to look at a Fill or a Polyline: an axis with an edge at a saturated value bounds nothing
-__device__ __forceinline__ bool SnapCandidate(const SnapQ &Q, uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) {
-    const bool bx = x0 != 0u && x1 != 0xffffu, by = y0 != 0u && y1 != 0xffffu;
-    return !(SnapBoxD2(Q, static_cast<double>(x0), static_cast<double>(y0), static_cast<double>(x1), static_cast<double>(y1), bx, by, bx, by) > Q.r2);
+// Is the ShortBbox of a Fill or a Polyline a reason to look at it: an axis with an edge at a saturated value bounds nothing
+__device__ __forceinline__ bool SnapCandidate(const SnapQ &Q, const ItemHead &h) {
+    const bool bx = h.x0 != 0u && h.x1 != 0xffffu, by = h.y0 != 0u && h.y1 != 0xffffu;
+    return !(SnapBoxD2(Q, static_cast<double>(h.x0), static_cast<double>(h.y0), static_cast<double>(h.x1), static_cast<double>(h.y1), bx, by, bx, by) > Q.r2);
 }
 
 // The wave's minimum of (d2, key), in every lane
@@ -196,68 +209,52 @@ __device__ __forceinline__ void SnapWaveMin(uint64_t &d2, uint64_t &key) {
 }  // namespace
 
 __global__ __launch_bounds__(kHitThreads) void pm_snap_kernel(SnapParams S) {
-    const HitParams &P = S.H;
+    const SceneView &V = S.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
-    for (uint32_t q = blockIdx.x * kHitWaves + WaveId(); q < P.n; q += n_waves) {
-        const float *in = S.xyr + static_cast<size_t>(q) * 3;
-        const uint32_t xb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[0]))));
-        const uint32_t yb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[1]))));
-        const uint32_t rb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[2]))));
-        const double r = static_cast<double>(__uint_as_float(rb));
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
+    const uint32_t n_waves = GridWaves();
+    for (uint32_t q = FirstWaveUnit(); q < S.n; q += n_waves) {
         SnapQ Q;
-        Q.x = static_cast<double>(__uint_as_float(xb));
-        Q.y = static_cast<double>(__uint_as_float(yb));
-        Q.r2 = r * r;
-        Q.vertices = (P.flags & kSnapVertices) != 0;
-        Q.edges = (P.flags & kSnapEdges) != 0;
-        // D21: a non-finite value, or r < 0, snaps to nothing
-        const bool valid = RectFiniteBits(xb) && RectFiniteBits(yb) && RectFiniteBits(rb) && !(r < 0.0);
+        const bool valid = SnapLoad(S.xyr + static_cast<size_t>(q) * 3, Q);
+        Q.vertices = (V.flags & kSnapVertices) != 0;
+        Q.edges = (V.flags & kSnapEdges) != 0;
         SnapBest bv, be;
-        for (uint32_t hi = P.n_items; hi != 0u && valid; hi = hi > 64u ? hi - 64u : 0u) {
+        for (uint32_t hi = V.n_items; hi != 0u && valid; hi = hi > 64u ? hi - 64u : 0u) {
             // lane 0 looks at the topmost item of the step
             bool cand = false;
             if (lane < hi) {
-                const uint32_t i = hi - 1u - lane;
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                const uint32_t w0 = LoadU32(it);
-                const uint32_t tag = w0 & 0xffffu;
-                const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-                const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
+                const ItemHead h = LoadItemHead(V, hi - 1u - lane);
+                const uint32_t i = h.item;
                 const bool taken_out = S.skip_items != nullptr && S.skip_items[i] != 0u;
                 if (taken_out) {
-                } else if (tag == kItemCircle) {
+                } else if (h.tag == kItemCircle) {
                     // D13's centre and radii, from the ShortBbox alone; the centre is exact in f32
-                    const double fx0 = static_cast<double>(x0), fy0 = static_cast<double>(y0);
-                    const double cx = (fx0 + static_cast<double>(x1)) * 0.5, cy = (fy0 + static_cast<double>(y1)) * 0.5;
-                    const bool offers = (w0 & kCircleEllipse) == 0u || (cx - fx0 > 0.0 && cy - fy0 > 0.0);
+                    const double fx0 = static_cast<double>(h.x0), fy0 = static_cast<double>(h.y0);
+                    const double cx = (fx0 + static_cast<double>(h.x1)) * 0.5, cy = (fy0 + static_cast<double>(h.y1)) * 0.5;
+                    const bool offers = (h.w0 & kCircleEllipse) == 0u || (cx - fx0 > 0.0 && cy - fy0 > 0.0);
                     if (Q.vertices && offers) SnapVertex(bv, Q, make_float2(static_cast<float>(cx), static_cast<float>(cy)), i, 0u);
-                } else if (tag == kItemLine) {
-                    if (!(skip && (LoadU32(it + 8) >> 24) == 0u)) {
-                        const float2 a = LoadF2(it + 16), b = LoadF2(it + 24);
+                } else if (h.tag == kItemLine) {
+                    if (!(skip && ItemTransparent(h))) {
+                        const float2 a = LoadF2(h.it + 16), b = LoadF2(h.it + 24);
                         if (Q.vertices) {
                             SnapVertex(bv, Q, a, i, 0u);
                             SnapVertex(bv, Q, b, i, 1u);
                         }
                         if (Q.edges) SnapEdge(be, Q, a, b, i, 0u);
                     }
-                } else if (tag == kItemFill) {
-                    cand = SnapCandidate(Q, x0, y0, x1, y1) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
-                } else if (tag == kItemPoly) {
+                } else if (h.tag == kItemFill) {
+                    cand = SnapCandidate(Q, h) && !(skip && ItemTransparent(h));
+                } else if (h.tag == kItemPoly) {
                     // (its box was made from the points and the width: of a width that is NaN or negative it bounds nothing)
-                    const bool boxed = __uint_as_float(LoadU32(it + 8)) >= 0.0f;
-                    cand = (!boxed || SnapCandidate(Q, x0, y0, x1, y1)) && !(skip && (LoadU32(it + 4) >> 24) == 0u);
+                    const bool boxed = __uint_as_float(LoadU32(h.it + 8)) >= 0.0f;
+                    cand = (!boxed || SnapCandidate(Q, h)) && !(skip && ItemTransparent(h));
                 }
             }
             uint64_t m = __ballot(cand);
             while (m != 0ull) {   // every candidate is finished: the nearest may be in any of them
-                const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-                m &= m - 1ull;
-                const uint32_t i = hi - 1u - l;
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                if ((LoadU32(it) & 0xffffu) == kItemFill) SnapFill(P, i, it, Q, lane, bv, be);
-                else SnapPoly(P, i, it, Q, lane, bv, be);
+                const ItemHead h = LoadItemHead(V, hi - 1u - TakeLowestLane(m));
+                if (h.tag == kItemFill) SnapFill(V, h.item, h.it, Q, lane, bv, be);
+                else SnapPoly(V, h.item, h.it, Q, lane, bv, be);
             }
         }
         // D21: a qualifying vertex wins over every edge
@@ -295,11 +292,6 @@ __global__ __launch_bounds__(kHitThreads) void pm_snap_kernel(SnapParams S) {
     }
 }
 
-// grid: what the chip holds at once (eight workgroups of four waves per CU), or a wave per query if that is less
-void LaunchSnap(const SnapParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n == 0u) return;
-    const uint32_t grid = min((p.H.n + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_snap_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
-}
+void LaunchSnap(const SnapParams &p, uint32_t n_cus, hipStream_t stream) { LaunchQuery(pm_snap_kernel, p, p.n, n_cus, stream); }
 
 }  // namespace pm

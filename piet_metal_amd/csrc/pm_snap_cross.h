@@ -1,7 +1,8 @@
 // pm_cross_kernel: snapping to intersections -- for every query {x, y, r} the nearest point within r of (x, y) where two edges of
 // the resident scene cross: which two edges, where on each, where, and how far.  Not on the frame path: like the other query
 // kernels it reads the scene and the scene index, nothing a frame writes.  Included by pm_context.hip after pm_snap.h, whose
-// query (SnapQ), edge distance (SnapEdge), culling (SnapBoxD2, SnapPass, SnapCandidate) and key (SnapKey) are used as they are.
+// query (SnapQ, SnapLoad), edge distance (SnapEdge), culling (SnapBoxD2, SnapPass, SnapCandidate) and key (SnapKey) are used as they
+// are; the item head and the chunk walk (ForItemChunks) are pm_query_common.h's.
 //
 // What an edge is, which edges are near, which pairs of them cross, where, and which pair wins is decision D23:
 // binary64 arithmetic, one rounding per written operation, in the written order (-ffp-contract=off) -- tests/np_cross.py states
@@ -31,12 +32,13 @@
 
 namespace pm {
 
-// One launch of pm_cross_kernel.  H: the scene, its index, the flags and the number of queries (H.xy, H.top_item, H.n_hit unused).
+// One launch of pm_cross_kernel
 struct CrossParams {
-    HitParams H;
+    SceneView V;
     const float *xyr;            // [3 n] {x, y, r}
     const uint32_t *skip_items;  // [n_items] a non-zero word takes the item out of the search (nullptr: none)
     uint8_t *out;                // [48 n] pm_snap_cross_result
+    uint32_t n;
 };
 
 namespace {
@@ -79,15 +81,15 @@ __device__ __forceinline__ void CrossAppend(CrossList &L, uint32_t &n_near, bool
 }
 
 // Fill item `item` (wave-uniform arguments): a lane notes which of its chunk's segments are near, the round's end stores them
-__device__ __forceinline__ void CrossFill(const HitParams &P, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, CrossList &L, uint32_t &n_near) {
+__device__ __forceinline__ void CrossFill(const SceneView &V, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, CrossList &L, uint32_t &n_near) {
     const uint32_t flags = LoadU32(it + 4), npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
     const bool compound = (flags & kFillCompound) != 0;
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     uint32_t noted = 0u, k0_noted = 0u;   // bit s: segment k0_noted + s is near, and seg[s] holds its ends
     float4 seg[kChunkSegs] = {};
     ForItemChunks(
-        P, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
+        V, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
         [&](uint32_t c) {
             const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, FillSegs(npt));
             k0_noted = k0;
@@ -111,14 +113,14 @@ __device__ __forceinline__ void CrossFill(const HitParams &P, uint32_t item, con
 }
 
 // Polyline item `item` of two points or more (one-point Polylines are evaluated on their item's lane)
-__device__ __forceinline__ void CrossPoly(const HitParams &P, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, CrossList &L, uint32_t &n_near) {
+__device__ __forceinline__ void CrossPoly(const SceneView &V, uint32_t item, const uint8_t *it, const SnapQ &Q, uint32_t lane, CrossList &L, uint32_t &n_near) {
     const uint32_t npt = LoadU32(it + 12);
-    const uint8_t *pts = P.scene + LoadU32(it + 16);
-    const uint32_t cb0 = P.chunk_base[item], cb1 = P.chunk_base[item + 1];
+    const uint8_t *pts = V.scene + LoadU32(it + 16);
+    const uint32_t cb0 = V.chunk_base[item], cb1 = V.chunk_base[item + 1];
     uint32_t noted = 0u, k0_noted = 0u;
     float4 seg[kChunkSegs] = {};
     ForItemChunks(
-        P, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
+        V, cb0, cb1, lane, [&](float4 bb) { return SnapPass(Q, bb); },
         [&](uint32_t c) {
             const uint32_t k0 = (c - cb0) * kChunkSegs, k1 = min(k0 + kChunkSegs, PolySegs(npt));
             k0_noted = k0;
@@ -201,72 +203,55 @@ __device__ __forceinline__ void CrossWaveMin(uint64_t &d2, uint64_t &key1, uint6
 
 __global__ __launch_bounds__(kHitThreads) void pm_cross_kernel(CrossParams S) {
     __shared__ CrossList s_list[kHitWaves];   // a slice per wave: no wave reads or writes another's
-    const HitParams &P = S.H;
+    const SceneView &V = S.V;
     const uint32_t lane = LaneId();
-    const uint32_t n_waves = gridDim.x * kHitWaves;
-    const bool skip = (P.flags & kHitSkipTransparent) != 0;
+    const bool skip = (V.flags & kHitSkipTransparent) != 0;
     CrossList &L = s_list[WaveId()];
-    for (uint32_t q = blockIdx.x * kHitWaves + WaveId(); q < P.n; q += n_waves) {
-        const float *in = S.xyr + static_cast<size_t>(q) * 3;
-        const uint32_t xb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[0]))));
-        const uint32_t yb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[1]))));
-        const uint32_t rb = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(__float_as_uint(in[2]))));
-        const double r = static_cast<double>(__uint_as_float(rb));
+    const uint32_t n_waves = GridWaves();
+    for (uint32_t q = FirstWaveUnit(); q < S.n; q += n_waves) {
         SnapQ Q;
-        Q.x = static_cast<double>(__uint_as_float(xb));
-        Q.y = static_cast<double>(__uint_as_float(yb));
-        Q.r2 = r * r;
+        const bool valid = SnapLoad(S.xyr + static_cast<size_t>(q) * 3, Q);
         Q.vertices = false;
         Q.edges = true;
-        // D23: a non-finite value, or r < 0, snaps to nothing
-        const bool valid = RectFiniteBits(xb) && RectFiniteBits(yb) && RectFiniteBits(rb) && !(r < 0.0);
         // ---- phase 1: the near list
         uint32_t n_near = 0u;   // (wave-uniform)
-        for (uint32_t hi = P.n_items; hi != 0u && valid; hi = hi > 64u ? hi - 64u : 0u) {
+        for (uint32_t hi = V.n_items; hi != 0u && valid; hi = hi > 64u ? hi - 64u : 0u) {
             // lane 0 looks at the topmost item of the step
             bool cand = false, one = false;   // one: this lane's item is a single near edge, a and b
             float2 a = make_float2(0.0f, 0.0f), b = a;
             if (lane < hi) {
-                const uint32_t i = hi - 1u - lane;
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                const uint32_t w0 = LoadU32(it);
-                const uint32_t tag = w0 & 0xffffu;
-                const uint2 bb = *reinterpret_cast<const uint2 *>(P.scene + P.bbox_ix + static_cast<size_t>(i) * sizeof(ShortBbox));
-                const uint32_t x0 = bb.x & 0xffffu, y0 = bb.x >> 16, x1 = bb.y & 0xffffu, y1 = bb.y >> 16;
-                const bool taken_out = S.skip_items != nullptr && S.skip_items[i] != 0u;
+                const ItemHead h = LoadItemHead(V, hi - 1u - lane);
+                const bool taken_out = S.skip_items != nullptr && S.skip_items[h.item] != 0u;
                 if (taken_out) {
-                } else if (tag == kItemLine) {
-                    if (!(skip && (LoadU32(it + 8) >> 24) == 0u)) {
-                        a = LoadF2(it + 16);
-                        b = LoadF2(it + 24);
+                } else if (h.tag == kItemLine) {
+                    if (!(skip && ItemTransparent(h))) {
+                        a = LoadF2(h.it + 16);
+                        b = LoadF2(h.it + 24);
                         one = CrossNear(Q, a, b);
                     }
-                } else if (tag == kItemFill) {
-                    cand = SnapCandidate(Q, x0, y0, x1, y1) && !(skip && (LoadU32(it + 8) >> 24) == 0u);
-                } else if (tag == kItemPoly) {
-                    const uint32_t npt = LoadU32(it + 12);
-                    const bool shown = !(skip && (LoadU32(it + 4) >> 24) == 0u);
+                } else if (h.tag == kItemFill) {
+                    cand = SnapCandidate(Q, h) && !(skip && ItemTransparent(h));
+                } else if (h.tag == kItemPoly) {
+                    const uint32_t npt = LoadU32(h.it + 12);
+                    const bool shown = !(skip && ItemTransparent(h));
                     if (npt == 1u) {   // one degenerate segment (the scene index has no chunk for it)
                         if (shown) {
-                            a = b = LoadF2(P.scene + LoadU32(it + 16));
+                            a = b = LoadF2(V.scene + LoadU32(h.it + 16));
                             one = CrossNear(Q, a, b);
                         }
                     } else if (npt != 0u) {
                         // (its box was made from the points and the width: of a width that is NaN or negative it bounds nothing)
-                        const bool boxed = __uint_as_float(LoadU32(it + 8)) >= 0.0f;
-                        cand = (!boxed || SnapCandidate(Q, x0, y0, x1, y1)) && shown;
+                        const bool boxed = __uint_as_float(LoadU32(h.it + 8)) >= 0.0f;
+                        cand = (!boxed || SnapCandidate(Q, h)) && shown;
                     }
                 }
             }
             CrossAppend(L, n_near, one, make_float4(a.x, a.y, b.x, b.y), hi - 1u - lane, 0u);
             uint64_t m = __ballot(cand);
             while (m != 0ull) {   // every candidate is finished: a near edge may be in any of them
-                const uint32_t l = static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
-                m &= m - 1ull;
-                const uint32_t i = hi - 1u - l;
-                const uint8_t *it = P.scene + P.items_ix + static_cast<size_t>(i) * kItemSize;
-                if ((LoadU32(it) & 0xffffu) == kItemFill) CrossFill(P, i, it, Q, lane, L, n_near);
-                else CrossPoly(P, i, it, Q, lane, L, n_near);
+                const ItemHead h = LoadItemHead(V, hi - 1u - TakeLowestLane(m));
+                if (h.tag == kItemFill) CrossFill(V, h.item, h.it, Q, lane, L, n_near);
+                else CrossPoly(V, h.item, h.it, Q, lane, L, n_near);
             }
         }
         WaveSync();   // the list is written: the wave reads it
@@ -309,10 +294,6 @@ __global__ __launch_bounds__(kHitThreads) void pm_cross_kernel(CrossParams S) {
 }
 
 // grid: LaunchSnap's rule (the workgroups beyond the three a CU's LDS holds at once wait their turn)
-void LaunchCross(const CrossParams &p, uint32_t n_cus, hipStream_t stream) {
-    if (p.H.n == 0u) return;
-    const uint32_t grid = min((p.H.n + kHitWaves - 1u) / kHitWaves, max(n_cus, 1u) * 8u);
-    hipLaunchKernelGGL(pm_cross_kernel, dim3(grid), dim3(kHitThreads), 0, stream, p);
-}
+void LaunchCross(const CrossParams &p, uint32_t n_cus, hipStream_t stream) { LaunchQuery(pm_cross_kernel, p, p.n, n_cus, stream); }
 
 }  // namespace pm

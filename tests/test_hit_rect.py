@@ -418,7 +418,9 @@ def test_cli_pick_tolerance_and_select(pm, tmp_path, capsys):
 
 def test_structural_constants_are_the_kernels():
     text = open(os.path.join(ROOT, "piet_metal_amd", "csrc", "pm_hit_rect.h")).read()
-    assert "hi > 64u ? hi - 64u : 0u" in text and "(P.n_items + 63u) / 64u" in text and "step * 64u + 64u" in text
+    assert "hi > 64u ? hi - 64u : 0u" in text and "ItemSteps(V.n_items)" in text and "step * 64u + 64u" in text
+    common = open(os.path.join(ROOT, "piet_metal_amd", "csrc", "pm_query_common.h")).read()   # (ItemSteps: the steps of 64 items)
+    assert "uint32_t ItemSteps(uint32_t n_items) { return (n_items + 63u) / 64u; }" in common
     assert rc.WAVE == 64 and rc.WALK_SIZES == (63, 64, 65, 129) and rc.LONG_CHUNKS == (64, 65, 513) and hs.CHUNK_SEGS == 4
     inc = open(os.path.join(ROOT, "include", "piet_metal_amd.h")).read()
     assert "#define PM_SEL_TOUCHES 1u" in inc and "#define PM_SEL_ENCLOSES 2u" in inc and "#define PM_ABI_VERSION 600" in inc

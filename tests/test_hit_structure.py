@@ -37,7 +37,8 @@ def test_structural_constants_are_pm_device_h():
     got = {k: int(v) for k, v in re.findall(r"^constexpr uint32_t (kChunkSegs|kSuperChunks) = (\d+);", text, re.M)}
     assert got == {"kChunkSegs": hs.CHUNK_SEGS, "kSuperChunks": hs.SUPER_CHUNKS}
     hit = open(os.path.join(ROOT, "piet_metal_amd", "csrc", "pm_hit_test.h")).read()
-    assert f"hi > {hs.WAVE}u ? hi - {hs.WAVE}u : 0u" in hit and f"gb += {hs.WAVE}u" in hit and f"cb1 - cb0 <= {hs.WAVE}u" in hit
+    chunks = open(os.path.join(ROOT, "piet_metal_amd", "csrc", "pm_query_common.h")).read()   # (ForItemChunks, shared by the query kernels)
+    assert f"hi > {hs.WAVE}u ? hi - {hs.WAVE}u : 0u" in hit and f"gb += {hs.WAVE}u" in chunks and f"cb1 - cb0 <= {hs.WAVE}u" in chunks
 
 
 # ---- CPU: the cases prove what they claim -------------------------------------------------------------------------
