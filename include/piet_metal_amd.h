@@ -554,6 +554,26 @@ int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *ite
  * ordered as pm_hit_test_device is. */
 int pm_select_rect_device(pm_ctx *c, const float rect[4], uint32_t flags, void *dev_item_flags, size_t cap, void *hip_stream);
 
+/* ==== hit stacks: the k topmost items under a point or a pick square (decision D24) ====
+ * Select-behind, "the objects under the cursor".  H = the items that contain point q as pm_hit_test means it (pm_hit_stack), or
+ * that rectangle q touches as pm_hit_rects means it (pm_hit_rects_stack), PM_HIT_SKIP_TRANSPARENT and invalid queries (a non-finite
+ * value, an inverted rectangle: H is empty) included, ordered topmost first: item index descending.  With PM_HIT_STOP_AT_OPAQUE the
+ * sequence ends at its first OPAQUE member, which is included: a Circle or ellipse always is, a Line, Fill or Polyline if the alpha
+ * byte of its colour is 255 (the stored byte and the geometric containment, not the frame's coverage: an item that covers a pixel
+ * partly still ends the stack); if no member is opaque the sequence is all of H.  m = its length.
+ * items[q * k + j] = its j-th member for j < min(k, m), PM_HIT_NONE for min(k, m) <= j < k: all k words of every query are written,
+ * none beyond n * k.  n_hit[q] (may be NULL) = m, not clipped by k.  With k = 1 and no PM_HIT_STOP_AT_OPAQUE, items and n_hit are
+ * pm_hit_test's (pm_hit_rects') top_item and n_hit.  PM_ERR_INVALID, before anything is enqueued: k == 0 or k > PM_HIT_STACK_MAX,
+ * flag bits other than these two, a NULL items or input with n > 0, no resident scene.  n == 0 is PM_OK.  Every other call refuses
+ * PM_HIT_STOP_AT_OPAQUE as an unknown bit.  Independent of the viewport as pm_hit_test is.  Synchronises. */
+#define PM_HIT_STOP_AT_OPAQUE 8u
+#define PM_HIT_STACK_MAX 256u
+int pm_hit_stack(pm_ctx *c, const float *xy, size_t n, uint32_t k, uint32_t flags, uint32_t *items /* n * k */, uint32_t *n_hit /* n, or NULL */);
+int pm_hit_rects_stack(pm_ctx *c, const float *rects /* n x {x0, y0, x1, y1} */, size_t n, uint32_t k, uint32_t flags, uint32_t *items, uint32_t *n_hit);
+/* Same on device memory, asynchronous on hip_stream (NULL: the context's stream), ordered as pm_hit_test_device is. */
+int pm_hit_stack_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream);
+int pm_hit_rects_stack_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream);
+
 /* ==== polygon queries: lasso selection, a marquee in a rotated view (decision D20) ====
  * The query polygon K has m vertices xy = m x {x, y} in scene coordinates, 3 <= m <= PM_POLYGON_MAX_VERTICES (else
  * PM_ERR_INVALID), and closes itself.  K TOUCHES an item if the item's outline reaches K's boundary, a point of the item lies in

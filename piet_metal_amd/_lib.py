@@ -43,6 +43,8 @@ PM_SVG_STROKE_DASHES = 16  # needs PM_SVG_STROKE_STYLES
 PM_FMT_RGBA8, PM_FMT_BGRA8 = 0, 1
 PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1
+PM_HIT_STOP_AT_OPAQUE = 8  # a flag of the stack calls
+PM_HIT_STACK_MAX = 256
 PM_SEL_TOUCHES = 1
 PM_SEL_ENCLOSES = 2
 PM_SEL_EVEN_ODD = 2  # a flag of the polygon calls
@@ -182,6 +184,10 @@ SIGNATURES = {
                                       C.c_void_p]),
     "pm_hit_rects": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_hit_rects_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_hit_stack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_hit_stack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_hit_rects_stack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_hit_rects_stack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_select_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32)]),
     "pm_select_rect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),

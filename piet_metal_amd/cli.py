@@ -8,6 +8,7 @@
     python -m piet_metal_amd.cli drawing.svg gone.png --frames 30 --fade            (the top-level groups fade out one after another)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick 3,3   (what is under these points?)
     python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-tolerance 3   (... or within 3 pixels of them?)
+    python -m piet_metal_amd.cli tiger out.png --pick 800,800 --pick-depth 4       (... and what lies behind it: up to four items, topmost first)
     python -m piet_metal_amd.cli tiger out.png --select 700,700,900,900    (marquee: what does this rectangle touch, what does it enclose?)
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12   (the nearest vertex, or else the nearest edge, within 12 pixels)
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12 --snap-to intersections   (the nearest point where two edges cross)
@@ -150,6 +151,7 @@ def main(argv=None) -> int:
     ap.add_argument("--fade", action="store_true", help="--frames N (>= 2): instead of spinning, the top-level groups of the document fade out one after another: frame k shows group g of G with opacity round(255 * clamp(1 - k / (N - 1) * G + g, 0, 1)); only the colours of the resident scene are rewritten on the device.  With --explode: both")
     ap.add_argument("--pick", action="append", default=[], metavar="X,Y", help="hit test: print the topmost item under this point (pixels) and the path it came from; may be repeated")
     ap.add_argument("--pick-tolerance", type=float, default=None, metavar="T", help="every --pick names the topmost item that comes within the square of half side T (pixels) around its point, instead of the item under the point itself")
+    ap.add_argument("--pick-depth", type=int, default=1, metavar="K", help="every --pick names up to K items (1 .. 256) under its point -- with --pick-tolerance: within the square around it --, topmost first, each with the path it came from: select-behind")
     ap.add_argument("--select", default=None, metavar="X0,Y0,X1,Y1", help="marquee selection: print every item the closed rectangle touches, occluded ones included, and the path it came from; items that lie wholly inside it are marked 'enclosed'")
     ap.add_argument("--lasso", default=None, metavar="X,Y,X,Y,...", help="lasso selection: the same for the polygon of these vertices (three or more, pixels), which closes itself, under the non-zero rule; an item is 'enclosed' if its outline lies inside and does not reach the polygon's boundary")
     ap.add_argument("--snap", action="append", default=[], metavar="X,Y", help="snapping: print the nearest vertex or point of an edge within --snap-radius of this point (pixels) -- the item, the path it came from, the vertex's or segment's index in the item, the point and its distance; may be repeated")
@@ -183,6 +185,8 @@ def main(argv=None) -> int:
             raise ValueError
     except ValueError:
         ap.error("--snap takes X,Y")
+    if not 1 <= args.pick_depth <= 256:
+        ap.error("--pick-depth takes 1 .. 256")
     if snaps and args.snap_radius is None:
         ap.error("--snap needs --snap-radius R")
     if args.explode is not None and args.frames < 2:
@@ -226,7 +230,15 @@ def main(argv=None) -> int:
             print(json.dumps(out))
         r.render()
         img = r.read_pixels()
-        if picks and args.pick_tolerance is None:  # one line per point: the item in flat paint order and the <path> it came from, or none
+        if picks and args.pick_depth > 1:  # one line per point: up to K items under it (or within the tolerance), topmost first
+            xy = np.array(picks, np.float32)
+            stack = r.hit_stack(xy, args.pick_depth) if args.pick_tolerance is None else r.pick_stack(xy, args.pick_tolerance, args.pick_depth)
+            of_item = r.item_paths()
+            tol = "" if args.pick_tolerance is None else f" +-{args.pick_tolerance:g}"
+            for (x, y), items in zip(picks, stack):
+                found = [f"item {int(t)} path {int(of_item[t])}" for t in items if t != 0xFFFFFFFF]
+                print(f"{x:g},{y:g}{tol}: " + (", ".join(found) if found else "none"))
+        elif picks and args.pick_tolerance is None:  # one line per point: the item in flat paint order and the <path> it came from, or none
             top = r.hit_test(np.array(picks, np.float32))
             of_item = r.item_paths()
             for (x, y), t in zip(picks, top):

@@ -39,6 +39,7 @@
 #include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
+#include "pm_hit_stack.h"  // pm_hit_stack_kernel, pm_hit_rects_stack_kernel: hit stacks (the k topmost items under a point or rectangle)
 #include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
 #include "pm_snap_cross.h" // pm_cross_kernel: snapping to intersections (the nearest crossing of two edges)
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
@@ -2860,10 +2861,12 @@ namespace {
 constexpr size_t kHitLaunchMax = static_cast<size_t>(1) << 30;  // queries per launch (the kernels index them in 32 bits)
 constexpr size_t kHitBatch = static_cast<size_t>(1) << 22;      // pm_hit_test, pm_hit_frame: queries staged on the device at a time (64 MiB)
 constexpr size_t kRectBatch = static_cast<size_t>(1) << 20;     // pm_hit_rects, pm_snap, pm_snap_intersections: the same (24 to 60 MiB)
+constexpr size_t kStackStageMax = kHitBatch * 16;               // pm_hit_stack, pm_hit_rects_stack: bytes staged at a time -- pm_hit_test's largest batch
 
 static_assert(PM_HIT_SKIP_TRANSPARENT == pm::kHitSkipTransparent && PM_HIT_NONE == pm::kHitNone && PM_SEL_TOUCHES == pm::kSelTouches &&
                   PM_SEL_ENCLOSES == pm::kSelEncloses && PM_POLYGON_MAX_VERTICES == pm::kPolyMaxVertices,
               "pm_query_common.h's and pm_hit_poly.h's constants are the header's");
+static_assert(PM_HIT_STOP_AT_OPAQUE == pm::kHitStopAtOpaque && PM_HIT_STACK_MAX == pm::kHitStackMax, "pm_hit_stack.h's constants are the header's");
 static_assert(PM_SNAP_VERTICES == pm::kSnapVertices && PM_SNAP_EDGES == pm::kSnapEdges && PM_SNAP_KIND_VERTEX == pm::kSnapKindVertex &&
                   PM_SNAP_KIND_EDGE == pm::kSnapKindEdge,
               "pm_snap.h's constants are the header's");
@@ -2886,6 +2889,15 @@ int HitCheck(pm_ctx *c, uint32_t flags) {
         return PM_ERR_INVALID;
     }
     return SceneResident(c);
+}
+
+// flags of a stack call: PM_HIT_STOP_AT_OPAQUE is theirs alone, the rest is HitCheck's
+int StackCheck(pm_ctx *c, uint32_t k, uint32_t flags) {
+    if (k == 0 || k > PM_HIT_STACK_MAX) {
+        SetError("pm_hit_stack: 1 <= k <= PM_HIT_STACK_MAX");
+        return PM_ERR_INVALID;
+    }
+    return HitCheck(c, flags & ~static_cast<uint32_t>(PM_HIT_STOP_AT_OPAQUE));
 }
 
 // What a kernel reads of the context: the scene and the scene index as they are now, and the call's flags
@@ -3219,6 +3231,76 @@ int pm_select_rect(pm_ctx *c, const float rect[4], uint32_t flags, uint32_t *ite
     const int r = HitCheck(c, flags);
     if (r != PM_OK) return r;
     return SelectToHost(c, item_flags, cap, n_touched, n_enclosed, [&](uint32_t *d_flags) { return SelectRectEnqueue(c, rect, flags, d_flags, c->stream); });
+}
+
+// ---- hit stacks (pm_hit_stack_kernel, pm_hit_rects_stack_kernel, pm_hit_stack.h; decision D24) ------------------------------
+extern "C++" {
+namespace {
+// The launches of either kernel for n queries of `in_floats` floats in device memory, on q: their params differ in the input's name alone
+template <typename Params>
+int StackEnqueue(pm_ctx *c, void (*launch)(const Params &, uint32_t, hipStream_t), const float *Params::*in, size_t in_floats, const float *d_in, size_t n,
+                 uint32_t k, uint32_t flags, uint32_t *d_items, uint32_t *d_cnt, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    Params p{};
+    p.V = QueryView(c, flags);
+    p.k = k;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.*in = d_in + in_floats * at;
+        p.items = d_items + at * k;
+        p.n_hit = d_cnt ? d_cnt + at : nullptr;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        launch(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+
+// The host-memory variant of either: {items, counts, queries} through the staging buffer, as many queries to a batch as kStackStageMax holds
+template <typename Params>
+int StackToHost(pm_ctx *c, void (*launch)(const Params &, uint32_t, hipStream_t), const float *Params::*in, size_t in_floats, const float *h_in, size_t n,
+                uint32_t k, uint32_t flags, uint32_t *items, uint32_t *n_hit) {
+    const size_t record = static_cast<size_t>(k) * 4;
+    return QueryBatches(c, h_in, in_floats * 4, n, kStackStageMax / (record + 4 + in_floats * 4), {items, record}, {n_hit, 4}, nullptr, 0,
+                        [&](uint8_t *d_in, size_t m, uint8_t *d_items, uint8_t *d_cnt, uint8_t *) {
+                            return StackEnqueue(c, launch, in, in_floats, reinterpret_cast<float *>(d_in), m, k, flags, reinterpret_cast<uint32_t *>(d_items),
+                                                reinterpret_cast<uint32_t *>(d_cnt), c->stream);
+                        });
+}
+}  // namespace
+}  // extern "C++"
+
+int pm_hit_stack_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream) {
+    if (!c || (n != 0 && (!dev_xy || !dev_items))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = StackCheck(c, k, flags);
+    if (r != PM_OK || n == 0) return r;
+    return StackEnqueue(c, pm::LaunchHitStack, &pm::HitStackParams::xy, 2, static_cast<const float *>(dev_xy), n, k, flags, static_cast<uint32_t *>(dev_items),
+                        static_cast<uint32_t *>(dev_n_hit), QueryStream(c, hip_stream));
+}
+
+int pm_hit_stack(pm_ctx *c, const float *xy, size_t n, uint32_t k, uint32_t flags, uint32_t *items, uint32_t *n_hit) {
+    if (!c || (n != 0 && (!xy || !items))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = StackCheck(c, k, flags);
+    if (r != PM_OK || n == 0) return r;
+    return StackToHost(c, pm::LaunchHitStack, &pm::HitStackParams::xy, 2, xy, n, k, flags, items, n_hit);
+}
+
+int pm_hit_rects_stack_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream) {
+    if (!c || (n != 0 && (!dev_rects || !dev_items))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = StackCheck(c, k, flags);
+    if (r != PM_OK || n == 0) return r;
+    return StackEnqueue(c, pm::LaunchHitRectsStack, &pm::HitRectStackParams::rects, 4, static_cast<const float *>(dev_rects), n, k, flags,
+                        static_cast<uint32_t *>(dev_items), static_cast<uint32_t *>(dev_n_hit), QueryStream(c, hip_stream));
+}
+
+int pm_hit_rects_stack(pm_ctx *c, const float *rects, size_t n, uint32_t k, uint32_t flags, uint32_t *items, uint32_t *n_hit) {
+    if (!c || (n != 0 && (!rects || !items))) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = StackCheck(c, k, flags);
+    if (r != PM_OK || n == 0) return r;
+    return StackToHost(c, pm::LaunchHitRectsStack, &pm::HitRectStackParams::rects, 4, rects, n, k, flags, items, n_hit);
 }
 
 // ---- polygon queries (pm_select_polygon_kernel, pm_hit_poly.h; decision D20) -------------------------------------------------

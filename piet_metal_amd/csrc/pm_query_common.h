@@ -1,5 +1,5 @@
-// What the query kernels share: pm_hit_test.h, pm_hit_frame.h, pm_hit_rect.h, pm_hit_poly.h, pm_snap.h, pm_snap_cross.h and
-// pm_bounds.h.  None of them is on the frame path: they read the scene and the scene index (pm_index_kernel), nothing a frame
+// What the query kernels share: pm_hit_test.h, pm_hit_frame.h, pm_hit_rect.h, pm_hit_poly.h, pm_hit_stack.h, pm_snap.h, pm_snap_cross.h
+// and pm_bounds.h.  None of them is on the frame path: they read the scene and the scene index (pm_index_kernel), nothing a frame
 // writes.  Included by pm_context.hip through those headers, in whose unit the kernels are compiled.
 //
 //  * SceneView: what a kernel reads of the context, the first member of every query's params (the host fills it in ONE place,
@@ -9,7 +9,7 @@
 //  * the item head: what a lane reads of the item it looks at (LoadItemHead, ItemTransparent);
 //  * the D13 predicates the later decisions reuse (HitWinding, HitStroke, HitCircle) and the finiteness tests;
 //  * ForItemChunks: a candidate's chunks spread over the lanes; TakeLowestLane: the next candidate of a step.
-// The item walks themselves -- topmost first (pm_hit_kernel, pm_hit_rects_kernel), every candidate of every step (pm_snap_kernel,
+// The item walks themselves -- topmost first (pm_hit_kernel, pm_hit_rects_kernel, the stack kernels), every candidate of every step (pm_snap_kernel,
 // pm_cross_kernel), a word per item with the steps dealt over the grid (pm_select_rect_kernel, pm_select_polygon_kernel) -- are
 // written out in the kernels over these pieces.  As templates over lambdas they were measured: every kernel that took one paid
 // two to four VGPRs, and pm_hit_rects_kernel, pm_cross_kernel and pm_select_polygon_kernel 1 .. 3 % of their time.

@@ -417,6 +417,71 @@ class Renderer:
         point (hit_rects on those squares, each value rounded to f32).  A hairline stroke can be clicked this way."""
         return self.hit_rects(self._pick_rects(points, tolerance), skip_transparent=skip_transparent, counts=counts)
 
+    # ---- hit stacks (decision D24) -----------------------------------------------------------
+    @staticmethod
+    def _stack_flags(skip_transparent, stop_at_opaque) -> int:
+        return (_lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0) | (_lib.PM_HIT_STOP_AT_OPAQUE if stop_at_opaque else 0)
+
+    def _stack(self, call, name, q, k, skip_transparent, stop_at_opaque, counts):
+        k = operator.index(k)
+        if not 1 <= k <= _lib.PM_HIT_STACK_MAX:
+            raise ValueError(f"{name} needs 1 <= k <= {_lib.PM_HIT_STACK_MAX}")
+        n = q.shape[0]
+        items = np.empty((n, k), np.uint32)
+        cnt = np.empty(n, np.uint32) if counts else None
+        flags = self._stack_flags(skip_transparent, stop_at_opaque)
+        _lib.check(call(self._h, q.ctypes.data, n, k, flags, items.ctypes.data, cnt.ctypes.data if counts else None), name)
+        return (items, cnt) if counts else items
+
+    def _stack_tensor(self, call, name, q, width, items, n_hit, stream, skip_transparent, stop_at_opaque) -> None:
+        if not (q.is_cuda and items.is_cuda) or str(q.dtype) != "torch.float32" or q.dim() != 2 or q.shape[1] != width or not q.is_contiguous():
+            raise TypeError(f"{name} needs a contiguous CUDA float32 tensor [n, {width}]")
+        n = q.shape[0]
+        if not (items.element_size() == 4 and not items.is_floating_point() and items.dim() == 2 and items.shape[0] == n and items.is_contiguous()):
+            raise TypeError(f"{name} writes a contiguous CUDA tensor [n, k] of 32-bit integers")
+        k = items.shape[1]
+        if not 1 <= k <= _lib.PM_HIT_STACK_MAX:
+            raise ValueError(f"{name} needs 1 <= k <= {_lib.PM_HIT_STACK_MAX}")
+        if n_hit is not None and not (n_hit.is_cuda and n_hit.element_size() == 4 and not n_hit.is_floating_point() and n_hit.numel() == n and n_hit.is_contiguous()):
+            raise TypeError(f"{name} writes the counts to a contiguous CUDA tensor of n 32-bit integers")
+        s = stream.cuda_stream if stream is not None else None
+        flags = self._stack_flags(skip_transparent, stop_at_opaque)
+        _lib.check(call(self._h, q.data_ptr(), n, k, flags, items.data_ptr(), n_hit.data_ptr() if n_hit is not None else None, s), name)
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def hit_stack(self, points, k: int, skip_transparent: bool = False, stop_at_opaque: bool = False, counts: bool = False):
+        """The k topmost items under every point, topmost first: uint32 [n, k], PM_HIT_NONE behind the last one -- select-behind, the
+        list of objects under a cursor.  `points` as in hit_test, 1 <= k <= PM_HIT_STACK_MAX (256).  stop_at_opaque: the list ends
+        at its first opaque item (a circle, or a colour of alpha 255), which is included: the chain of items between the eye and
+        the first opaque one.  With counts=True also the full length of each list, uint32 [n], not clipped by k."""
+        xy = np.ascontiguousarray(points, dtype=np.float32)
+        if xy.ndim != 2 or xy.shape[1] != 2:
+            raise ValueError("hit_stack needs an (n, 2) array of points")
+        return self._stack(self._lib.pm_hit_stack, "pm_hit_stack", xy, k, skip_transparent, stop_at_opaque, counts)
+
+    def hit_stack_tensor(self, xy, items, n_hit=None, stream=None, skip_transparent: bool = False, stop_at_opaque: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: xy float32 [n, 2], items int32 or uint32 [n, k] (k = items.shape[1]), n_hit
+        [n], all contiguous.  `stream` as in hit_test_tensor."""
+        self._stack_tensor(self._lib.pm_hit_stack_device, "pm_hit_stack_device", xy, 2, items, n_hit, stream, skip_transparent, stop_at_opaque)
+
+    def hit_rects_stack(self, rects, k: int, skip_transparent: bool = False, stop_at_opaque: bool = False, counts: bool = False):
+        """The k topmost items every rectangle touches, topmost first: hit_stack for the rectangles of hit_rects."""
+        rc = np.ascontiguousarray(rects, dtype=np.float32)
+        if rc.ndim != 2 or rc.shape[1] != 4:
+            raise ValueError("hit_rects_stack needs an (n, 4) array of rectangles")
+        return self._stack(self._lib.pm_hit_rects_stack, "pm_hit_rects_stack", rc, k, skip_transparent, stop_at_opaque, counts)
+
+    def hit_rects_stack_tensor(self, rects, items, n_hit=None, stream=None, skip_transparent: bool = False, stop_at_opaque: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: rects float32 [n, 4], items [n, k], n_hit [n].  `stream` as in hit_test_tensor."""
+        self._stack_tensor(self._lib.pm_hit_rects_stack_device, "pm_hit_rects_stack_device", rects, 4, items, n_hit, stream, skip_transparent, stop_at_opaque)
+
+    def pick_stack(self, points, tolerance, k: int, skip_transparent: bool = False, stop_at_opaque: bool = False, counts: bool = False):
+        """hit_stack with a tolerance: the k topmost items that come within the square of half side `tolerance` around each point
+        (hit_rects_stack on pick's squares)."""
+        return self.hit_rects_stack(self._pick_rects(points, tolerance), k, skip_transparent=skip_transparent, stop_at_opaque=stop_at_opaque, counts=counts)
+
     def select_rect(self, x0, y0, x1, y1, skip_transparent: bool = False):
         """Marquee selection: (touched, enclosed), bool arrays over the items in flat paint order -- every item the closed rectangle
         touches, occluded ones included, and every item that lies wholly inside it."""
