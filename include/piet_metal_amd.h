@@ -686,6 +686,56 @@ int pm_union_bounds_device(pm_ctx *c, uint32_t flags,
                            const void *dev_label_of_item, size_t n_label_words, uint32_t n_labels,
                            void *dev_out, void *hip_stream);
 
+/* ==== path measurement: lengths and points at a length (decision D25) ====
+ * Lengths are unsigned 64-bit integers in units of 2^-16 px, D15's: a segment's is min(floor(len * 65536 + 0.5), 2^32) of its
+ * binary64 length (0 if that is a NaN), an item's the sum over its segments.  The segments of an item are named by their index k
+ * as pm_snap names edges: a Line has segment 0, a Polyline k from point k to point k + 1, a Fill every entry that starts a segment,
+ * closing ones included, a compound Fill's sub-paths one after another.  A Circle, an ellipse, a Fill of no points, an item
+ * PM_HIT_SKIP_TRANSPARENT skips and an item index >= n_items have kind PM_MEASURE_NONE, no segment and length 0.  A styled or
+ * dashed stroke is the outline Fill it is; a circle's circumference is not offered.
+ *
+ * pm_item_lengths: one record {length, n_segments, kind} per item in flat paint order.  Output discipline is pm_item_bounds':
+ * *n_items (may be NULL) is always set; PM_ERR_CAPACITY if cap < n_items, and then nothing is written.  Synchronises.
+ *
+ * pm_points_at_length: out[k] = the point at position q[k].s (any u64) along item q[k].item, on the segment `index` whose
+ * [Q, Q + q) holds s (only segments of a length own positions): {x, y} = a + (b - a) * t in binary64, rounded once, t the
+ * parameter along the segment, {tx, ty} the unit direction of the segment.  s beyond the item's length T answers with the end of
+ * the last segment of a length (t = 1) and PM_MEASURE_CLAMPED iff s > T.  An item of length 0 that has a point answers with its
+ * first point, t = 0, direction (0, 0), PM_MEASURE_FOUND | PM_MEASURE_DEGENERATE (and PM_MEASURE_CLAMPED iff s > 0).  An item
+ * without a walk or without a point: item = PM_HIT_NONE and every other byte 0.  If the located segment has a non-finite end,
+ * item, status and index are as defined and the five floats are unspecified.
+ *
+ * pm_positions_on_edges: the inverse -- out[k].s = Q_index + min(floor(t * q_index + 0.5), q_index) for the point at parameter t
+ * of segment `index` of the item, what pm_snap reports as (item, index, t) for an edge and (item, index, 0) for a vertex of a
+ * Polyline or a Line; status PM_MEASURE_FOUND.  An index that names no segment of the item, t outside [0, 1] or a NaN:
+ * item = PM_HIT_NONE and every other byte 0.
+ *
+ * flags: PM_HIT_SKIP_TRANSPARENT or 0.  PM_ERR_INVALID, before anything is enqueued: any other flag bit, no resident scene, a NULL
+ * q or out with n != 0, a query whose `reserved` is not 0 (the _device variants cannot look: there such a query answers
+ * PM_HIT_NONE).  n == 0 is PM_OK and writes nothing; records beyond n are not written.  Independent of the viewport; frames in
+ * flight are not disturbed.  Synchronise. */
+#define PM_MEASURE_NONE 0u         /* pm_item_length.kind */
+#define PM_MEASURE_OPEN 1u
+#define PM_MEASURE_CLOSED 2u
+#define PM_MEASURE_FOUND 1u        /* status bits */
+#define PM_MEASURE_CLAMPED 2u
+#define PM_MEASURE_DEGENERATE 4u
+typedef struct { uint64_t length; uint32_t n_segments, kind; } pm_item_length;                             /* 16 bytes */
+typedef struct { uint32_t item, reserved; uint64_t s; } pm_length_query;                                   /* 16 bytes */
+typedef struct { uint32_t item, status, index; float t; float x, y; float tx, ty; } pm_length_point;       /* 32 bytes */
+typedef struct { uint32_t item, index; float t; uint32_t reserved; } pm_edge_query;                        /* 16 bytes */
+typedef struct { uint64_t s; uint32_t item, status; } pm_length_at;                                        /* 16 bytes */
+
+int pm_item_lengths(pm_ctx *c, uint32_t flags, pm_item_length *out, size_t cap, uint32_t *n_items);
+int pm_points_at_length(pm_ctx *c, const pm_length_query *q, size_t n, uint32_t flags, pm_length_point *out);
+int pm_positions_on_edges(pm_ctx *c, const pm_edge_query *q, size_t n, uint32_t flags, pm_length_at *out);
+/* Same on device memory (every pointer 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is.  A pm_snap_result {item, kind, index, t, ...} becomes a pm_edge_query {item, index, t, 0} by moving three
+ * of its words, which can be done on the device: no read-back stands between a snap and its position. */
+int pm_item_lengths_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap, void *hip_stream);
+int pm_points_at_length_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream);
+int pm_positions_on_edges_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

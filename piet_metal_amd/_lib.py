@@ -53,6 +53,8 @@ PM_SNAP_VERTICES, PM_SNAP_EDGES = 2, 4
 PM_SNAP_KIND_VERTEX, PM_SNAP_KIND_EDGE = 1, 2
 PM_SNAP_KIND_INTERSECTION, PM_SNAP_KIND_TOO_MANY = 3, 4
 PM_SNAP_MAX_NEAR_EDGES = 512
+PM_MEASURE_NONE, PM_MEASURE_OPEN, PM_MEASURE_CLOSED = 0, 1, 2  # pm_item_length.kind
+PM_MEASURE_FOUND, PM_MEASURE_CLAMPED, PM_MEASURE_DEGENERATE = 1, 2, 4  # status bits of the measure records
 
 
 class PathEl(C.Structure):
@@ -203,6 +205,12 @@ SIGNATURES = {
     "pm_union_bounds": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "pm_union_bounds_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p,
                                          C.c_void_p]),
+    "pm_item_lengths": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "pm_item_lengths_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_points_at_length": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "pm_points_at_length_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_positions_on_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
+    "pm_positions_on_edges_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

@@ -13,6 +13,7 @@
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12   (the nearest vertex, or else the nearest edge, within 12 pixels)
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12 --snap-to intersections   (the nearest point where two edges cross)
     python -m piet_metal_amd.cli tiger out.png --bounds --select 700,700,900,900   (where is the picture, where the selection, and how many items)
+    python -m piet_metal_amd.cli tiger out.png --lengths --point-at 40,37.5        (how long every path is; the point and the tangent 37.5 px along item 40)
     python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -112,6 +113,19 @@ def print_snaps(r, points, radius, to) -> None:
         print(head + f"item {int(s['item'])} path {int(of_item[s['item']])} {what} at {float(s['x']):.9g},{float(s['y']):.9g} d2 {float(s['d2']):.17g}")
 
 
+def print_points_at(r, asks) -> None:
+    """--point-at: one line per (item, distance in pixels)."""
+    rec = r.points_at_length([a[0] for a in asks], [a[1] for a in asks])
+    of_item = r.item_paths()
+    for (i, d), p in zip(asks, rec):
+        head = f"item {i} at {d:g}: "
+        if p["item"] == 0xFFFFFFFF:
+            print(head + "none")
+            continue
+        print(head + f"point {float(p['x']):g},{float(p['y']):g} tangent {float(p['tx']):g},{float(p['ty']):g} segment {int(p['index'])} "
+              f"t {float(p['t']):g} path {int(of_item[i])}" + (" (clamped)" if p["status"] & 2 else ""))
+
+
 def bounds_record(r, words=None) -> dict:
     """--bounds: the box and the counts of the whole scene (words None) or of the items whose word is non-zero."""
     box, n_items, n_boxed = r.selection_bounds(words)
@@ -160,7 +174,15 @@ def main(argv=None) -> int:
     ap.add_argument("--bounds", action="store_true", help="bounds: print one JSON line with the box {x0, y0, x1, y1} (pixels) of everything that is drawn and how many items it has -- \"scene\" -- and, with --select / --lasso, the same for the items the query touches -- \"selection\"; with --fit: of the fitted view")
     ap.add_argument("--fit", action="store_true", help="zoom to fit: before rendering, change the view so that the box of everything drawn -- with --select / --lasso: of what the query touches in the view as given -- fills the output, centred; what --select / --lasso print is what they touched in the view as given")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
+    ap.add_argument("--lengths", action="store_true", help="path measurement: print one JSON line {\"paths\": [{\"length\", \"n_items\"}, ...]} -- per path the length in pixels of the geometry it draws (flattened curves, the outlines of styled and dashed strokes, closing segments included) and how many items that is")
+    ap.add_argument("--point-at", action="append", default=[], metavar="ITEM,DIST", help="path measurement: print the point DIST pixels along item ITEM, the unit tangent there, the segment it lies on with the parameter along it, and the path the item came from; beyond the item's end: its end, marked (clamped); may be repeated")
     args = ap.parse_args(argv)
+    try:
+        points_at = [(int(p.split(",")[0]), float(p.split(",")[1])) for p in args.point_at]
+        if any(len(p.split(",")) != 2 for p in args.point_at) or any(i < 0 or i > 0xFFFFFFFF for i, _ in points_at):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--point-at takes ITEM,DIST")
     try:
         picks = [tuple(float(v) for v in p.split(",")) for p in args.pick]
         if any(len(p) != 2 for p in picks):
@@ -254,6 +276,11 @@ def main(argv=None) -> int:
             print_selection(r, lasso, *lassoed)
         if snaps:  # one line per point: the record, and the <path> the item came from
             print_snaps(r, snaps, args.snap_radius, args.snap_to)
+        if args.lengths:  # one JSON line: per path its length in pixels and its item count
+            lengths, counts = r.path_lengths()
+            print(json.dumps({"paths": [{"length": v / 65536, "n_items": c} for v, c in zip(lengths, counts)]}))
+        if points_at:  # one line per query: the record, and the <path> the item came from
+            print_points_at(r, points_at)
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

@@ -43,6 +43,7 @@
 #include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
 #include "pm_snap_cross.h" // pm_cross_kernel: snapping to intersections (the nearest crossing of two edges)
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
+#include "pm_measure.h"    // pm_item_lengths_kernel, pm_points_at_length_kernel, pm_positions_on_edges_kernel: path measurement
 #include "pm_layout.h"
 
 namespace {
@@ -3558,6 +3559,164 @@ int pm_union_bounds(pm_ctx *c, uint32_t flags, const uint32_t *item_words, size_
     PM_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
     PM_TRY(hipStreamSynchronize(c->stream));
     return PM_OK;
+}
+
+// ---- path measurement (pm_measure.h; decision D25) ----------------------------------------------------------------------------------
+namespace {
+static_assert(PM_MEASURE_NONE == pm::kMeasureNone && PM_MEASURE_OPEN == pm::kMeasureOpen && PM_MEASURE_CLOSED == pm::kMeasureClosed &&
+                  PM_MEASURE_FOUND == pm::kMeasureFound && PM_MEASURE_CLAMPED == pm::kMeasureClamped && PM_MEASURE_DEGENERATE == pm::kMeasureDegenerate,
+              "pm_measure.h's constants are the header's");
+static_assert(sizeof(pm_item_length) == 16 && offsetof(pm_item_length, length) == 0 && offsetof(pm_item_length, n_segments) == 8 &&
+                  offsetof(pm_item_length, kind) == 12,
+              "the record pm_item_lengths_kernel writes");
+static_assert(sizeof(pm_length_query) == 16 && offsetof(pm_length_query, item) == 0 && offsetof(pm_length_query, reserved) == 4 && offsetof(pm_length_query, s) == 8 &&
+                  sizeof(pm_edge_query) == 16 && offsetof(pm_edge_query, item) == 0 && offsetof(pm_edge_query, index) == 4 && offsetof(pm_edge_query, t) == 8 &&
+                  offsetof(pm_edge_query, reserved) == 12,
+              "the queries the measure kernels read");
+static_assert(sizeof(pm_length_point) == 32 && offsetof(pm_length_point, item) == 0 && offsetof(pm_length_point, status) == 4 &&
+                  offsetof(pm_length_point, index) == 8 && offsetof(pm_length_point, t) == 12 && offsetof(pm_length_point, x) == 16 &&
+                  offsetof(pm_length_point, y) == 20 && offsetof(pm_length_point, tx) == 24 && offsetof(pm_length_point, ty) == 28 &&
+                  sizeof(pm_length_at) == 16 && offsetof(pm_length_at, s) == 0 && offsetof(pm_length_at, item) == 8 && offsetof(pm_length_at, status) == 12,
+              "the records the measure kernels write");
+
+constexpr size_t kMeasureBatch = static_cast<size_t>(1) << 20;   // pm_points_at_length, pm_positions_on_edges: queries staged at a time (32 to 48 MiB)
+
+// Everything the two per-query calls refuse, before anything is enqueued
+int MeasureCheck(pm_ctx *c, const char *name, const void *q, size_t n, uint32_t flags, const void *out) {
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (n != 0 && (!q || !out)) {
+        SetError(std::string(name) + ": a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+int MeasureAligned(const char *name, const void *a, const void *b) {
+    if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 7u) != 0) {
+        SetError(std::string(name) + ": a device pointer is not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+int ItemLengthsEnqueue(pm_ctx *c, uint32_t flags, uint8_t *d_out, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::MeasureParams p{};
+    p.V = QueryView(c, flags);
+    p.out = d_out;
+    pm::LaunchItemLengths(p, static_cast<uint32_t>(c->n_cus), q);
+    return QueryOrderBehind(c, q);
+}
+
+// The launches of either per-query kernel for n queries of 16 bytes in device memory, on q
+int MeasureEnqueue(pm_ctx *c, void (*launch)(const pm::MeasureParams &, uint32_t, hipStream_t), size_t record, const uint8_t *d_q, size_t n, uint32_t flags,
+                   uint8_t *d_out, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::MeasureParams p{};
+    p.V = QueryView(c, flags);
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.q = d_q + 16 * at;
+        p.out = d_out + record * at;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        launch(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+
+// The host-memory variant of either: {records, queries} through the staging buffer
+int MeasureToHost(pm_ctx *c, void (*launch)(const pm::MeasureParams &, uint32_t, hipStream_t), size_t record, const void *q, size_t n, uint32_t flags, void *out) {
+    return QueryBatches(c, q, 16, n, kMeasureBatch, {out, record}, {nullptr, 0}, nullptr, 0, [&](uint8_t *d_in, size_t m, uint8_t *d_out, uint8_t *, uint8_t *) {
+        return MeasureEnqueue(c, launch, record, d_in, m, flags, d_out, c->stream);
+    });
+}
+}  // namespace
+
+int pm_item_lengths_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    if (cap < c->n_items) return PM_ERR_CAPACITY;
+    if (c->n_items == 0) return PM_OK;
+    if (!dev_out || (reinterpret_cast<uintptr_t>(dev_out) & 7u) != 0) {
+        SetError("pm_item_lengths_device: dev_out is NULL or not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return ItemLengthsEnqueue(c, flags, static_cast<uint8_t *>(dev_out), QueryStream(c, hip_stream));
+}
+
+int pm_item_lengths(pm_ctx *c, uint32_t flags, pm_item_length *out, size_t cap, uint32_t *n_items) {
+    if (!c) return PM_ERR_INVALID;
+    if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK) return r;
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n == 0) return PM_OK;
+    if (!out) {
+        SetError("pm_item_lengths: out is NULL");
+        return PM_ERR_INVALID;
+    }
+    PM_TRY(QueryStaging(c, n * sizeof(pm_item_length)));
+    r = ItemLengthsEnqueue(c, flags, c->d_stage, c->stream);
+    if (r != PM_OK) return r;
+    PM_TRY(hipMemcpyAsync(out, c->d_stage, n * sizeof(pm_item_length), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
+    return PM_OK;
+}
+
+int pm_points_at_length_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = MeasureCheck(c, "pm_points_at_length", dev_q, n, flags, dev_out);
+    if (r != PM_OK || n == 0) return r;
+    r = MeasureAligned("pm_points_at_length_device", dev_q, dev_out);
+    if (r != PM_OK) return r;
+    return MeasureEnqueue(c, pm::LaunchPointsAtLength, sizeof(pm_length_point), static_cast<const uint8_t *>(dev_q), n, flags, static_cast<uint8_t *>(dev_out),
+                          QueryStream(c, hip_stream));
+}
+
+int pm_points_at_length(pm_ctx *c, const pm_length_query *q, size_t n, uint32_t flags, pm_length_point *out) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = MeasureCheck(c, "pm_points_at_length", q, n, flags, out);
+    if (r != PM_OK || n == 0) return r;
+    for (size_t k = 0; k < n; ++k) {
+        if (q[k].reserved != 0u) {
+            SetError("pm_points_at_length: a query's reserved word is not 0");
+            return PM_ERR_INVALID;
+        }
+    }
+    return MeasureToHost(c, pm::LaunchPointsAtLength, sizeof(*out), q, n, flags, out);
+}
+
+int pm_positions_on_edges_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = MeasureCheck(c, "pm_positions_on_edges", dev_q, n, flags, dev_out);
+    if (r != PM_OK || n == 0) return r;
+    r = MeasureAligned("pm_positions_on_edges_device", dev_q, dev_out);
+    if (r != PM_OK) return r;
+    return MeasureEnqueue(c, pm::LaunchPositionsOnEdges, sizeof(pm_length_at), static_cast<const uint8_t *>(dev_q), n, flags, static_cast<uint8_t *>(dev_out),
+                          QueryStream(c, hip_stream));
+}
+
+int pm_positions_on_edges(pm_ctx *c, const pm_edge_query *q, size_t n, uint32_t flags, pm_length_at *out) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = MeasureCheck(c, "pm_positions_on_edges", q, n, flags, out);
+    if (r != PM_OK || n == 0) return r;
+    for (size_t k = 0; k < n; ++k) {
+        if (q[k].reserved != 0u) {
+            SetError("pm_positions_on_edges: a query's reserved word is not 0");
+            return PM_ERR_INVALID;
+        }
+    }
+    return MeasureToHost(c, pm::LaunchPositionsOnEdges, sizeof(*out), q, n, flags, out);
 }
 
 int pm_item_paths(pm_ctx *c, uint32_t *path_of_item, size_t cap, uint32_t *n_items) {

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import ctypes as C
 import operator
+from fractions import Fraction
 
 import numpy as np
 
@@ -33,6 +34,24 @@ assert SNAP_CROSS_DTYPE.itemsize == 48
 # pm_label_bounds (decision D22): what Renderer.union_bounds returns, 40 bytes a record
 LABEL_BOUNDS_DTYPE = np.dtype([("box", "<f8", (4,)), ("n_items", "<u4"), ("n_boxed", "<u4")])
 assert LABEL_BOUNDS_DTYPE.itemsize == 40
+# the records and queries of path measurement (decision D25): lengths and positions are integers in units of 2^-16 px
+ITEM_LENGTH_DTYPE = np.dtype([("length", "<u8"), ("n_segments", "<u4"), ("kind", "<u4")])
+LENGTH_QUERY_DTYPE = np.dtype([("item", "<u4"), ("reserved", "<u4"), ("s", "<u8")])
+LENGTH_POINT_DTYPE = np.dtype([("item", "<u4"), ("status", "<u4"), ("index", "<u4"), ("t", "<f4"), ("x", "<f4"), ("y", "<f4"), ("tx", "<f4"), ("ty", "<f4")])
+EDGE_QUERY_DTYPE = np.dtype([("item", "<u4"), ("index", "<u4"), ("t", "<f4"), ("reserved", "<u4")])
+LENGTH_AT_DTYPE = np.dtype([("s", "<u8"), ("item", "<u4"), ("status", "<u4")])
+assert (ITEM_LENGTH_DTYPE.itemsize, LENGTH_QUERY_DTYPE.itemsize, LENGTH_POINT_DTYPE.itemsize, EDGE_QUERY_DTYPE.itemsize, LENGTH_AT_DTYPE.itemsize) == (16, 16, 32, 16, 16)
+LENGTH_UNIT = 65536  # units of a length per pixel
+
+
+def length_units(px) -> int:
+    """D15's fix: a distance in pixels as a position in units of 2^-16 px -- min(floor(px * 65536 + 0.5), 2^64 - 1), 0 for a NaN or a
+    negative value."""
+    v = np.float64(px)
+    if not v > 0:
+        return 0
+    f = np.floor(v * np.float64(LENGTH_UNIT) + 0.5)
+    return (1 << 64) - 1 if f >= 2.0 ** 64 else int(f)
 
 
 def _warn_default_stream() -> None:
@@ -733,6 +752,136 @@ class Renderer:
         if groups is None:
             return self.union_bounds(None, 1, item_flags, mask, skip_transparent)
         return self.union_bounds(groups[of_item], int(groups.max()) + 1 if len(groups) else 1, item_flags, mask, skip_transparent)
+
+    # ---- path measurement (decision D25) ---------------------------------------------------
+    def item_lengths(self, skip_transparent: bool = False) -> np.ndarray:
+        """How long every item is, in flat paint order: a structured array (ITEM_LENGTH_DTYPE) of n_items records -- `length` in units
+        of 2^-16 px (divide by LENGTH_UNIT for pixels), `n_segments`, and `kind` 1 for an open walk (Line, Polyline), 2 for a closed
+        one (Fill: closing segments count), 0 for an item that has none (a Circle, an ellipse, a Fill of no points, and with
+        skip_transparent an item of alpha 0).  It is the geometry that is drawn: flattened curves under their groups' affines, a
+        styled or dashed stroke's outline."""
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        out = np.zeros(self.stats()["n_items"], ITEM_LENGTH_DTYPE)
+        _lib.check(self._lib.pm_item_lengths(self._h, flags, out.ctypes.data, len(out), None), "pm_item_lengths")
+        return out
+
+    def item_lengths_tensor(self, out, stream=None, skip_transparent: bool = False) -> None:
+        """The same into a torch CUDA tensor, asynchronous: out int32 [m, 4] with m >= n_items, contiguous (the 16-byte records:
+        out.cpu().numpy().view(ITEM_LENGTH_DTYPE)); rows beyond n_items are not written.  `stream` as in hit_test_tensor."""
+        if not (out.is_cuda and str(out.dtype) == "torch.int32" and out.dim() == 2 and out.shape[1] == 4 and out.is_contiguous()):
+            raise TypeError("item_lengths_tensor writes a contiguous CUDA int32 tensor [m, 4]")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_item_lengths_device(self._h, flags, out.data_ptr(), out.shape[0], s), "pm_item_lengths_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def points_at_units(self, items, positions, skip_transparent: bool = False) -> np.ndarray:
+        """points_at_length with the positions given as integers in units of 2^-16 px (any value below 2^64)."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        q = np.zeros(len(it), LENGTH_QUERY_DTYPE)
+        q["item"] = it
+        pos = np.asarray(positions, dtype=np.uint64) if not isinstance(positions, (list, tuple)) else np.array([int(p) for p in positions], dtype=np.uint64)
+        if pos.ndim not in (0, 1) or (pos.ndim == 1 and len(pos) != len(it)):
+            raise ValueError("one position, or one per item")
+        q["s"] = pos
+        out = np.zeros(len(q), LENGTH_POINT_DTYPE)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_points_at_length(self._h, q.ctypes.data, len(q), flags, out.ctypes.data), "pm_points_at_length")
+        return out
+
+    def points_at_length(self, items, distances_px, skip_transparent: bool = False) -> np.ndarray:
+        """The point at a distance along an item, for every pair (items[k], distances_px[k]): a structured array
+        (LENGTH_POINT_DTYPE) -- `x, y` the point, `tx, ty` the unit direction of the path there, `index` the segment it lies on (what
+        snap calls an edge's index) and `t` the parameter along that segment; `status` has bit 1 (found), bit 2 if the distance
+        was beyond the item's end and the answer is the end, bit 4 if the item has a point and no length (direction (0, 0)).  `item` is
+        PM_HIT_NONE for an item without a walk.  A distance is rounded to units of 2^-16 px (length_units); a negative one or a NaN
+        is 0."""
+        d = np.asarray(distances_px, dtype=np.float64)
+        n = len(np.atleast_1d(np.asarray(items)))
+        if d.ndim not in (0, 1) or (d.ndim == 1 and len(d) != n):
+            raise ValueError("one distance, or one per item")
+        units = [length_units(v) for v in np.broadcast_to(d, (n,))]
+        return self.points_at_units(items, units, skip_transparent)
+
+    def points_at_fraction(self, items, fractions, skip_transparent: bool = False) -> np.ndarray:
+        """points_at_length at the fraction f of every item's own length: position floor(f * T + 0.5) in Python integers, T from
+        item_lengths; f is clamped to [0, 1] (a NaN is 0)."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        f = np.asarray(fractions, dtype=np.float64)
+        if f.ndim not in (0, 1) or (f.ndim == 1 and len(f) != len(it)):
+            raise ValueError("one fraction, or one per item")
+        total = self.item_lengths(skip_transparent)["length"]
+        units = []
+        for i, v in zip(it.tolist(), np.broadcast_to(f, (len(it),)).tolist()):
+            T = int(total[i]) if i < len(total) else 0
+            num, den = Fraction(min(max(v, 0.0), 1.0) if v == v else 0.0).as_integer_ratio()
+            units.append((2 * num * T + den) // (2 * den))   # floor(f T + 1/2), exactly
+        return self.points_at_units(it, units, skip_transparent)
+
+    def points_at_length_tensor(self, queries, out, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: queries int32 [n, 4] (the 16-byte LENGTH_QUERY_DTYPE records {item, 0, s low,
+        s high}), out int32 [n, 8] (out.cpu().numpy().view(LENGTH_POINT_DTYPE)), both contiguous.  `stream` as in hit_test_tensor."""
+        if not (queries.is_cuda and out.is_cuda) or str(queries.dtype) != "torch.int32" or queries.dim() != 2 or queries.shape[1] != 4 or not queries.is_contiguous():
+            raise TypeError("points_at_length_tensor needs a contiguous CUDA int32 tensor [n, 4]")
+        n = queries.shape[0]
+        if str(out.dtype) != "torch.int32" or tuple(out.shape) != (n, 8) or not out.is_contiguous():
+            raise TypeError("points_at_length_tensor writes a contiguous CUDA int32 tensor [n, 8]")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_points_at_length_device(self._h, queries.data_ptr(), n, flags, out.data_ptr(), s), "pm_points_at_length_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def positions_on_edges(self, items, indices, ts, skip_transparent: bool = False) -> np.ndarray:
+        """How far along its item a point of an edge is -- the inverse of points_at_length, for what snap reports as (item, index, t):
+        a structured array (LENGTH_AT_DTYPE) with `s` in units of 2^-16 px and `status` 1; `item` is PM_HIT_NONE (and s 0) where
+        `index` names no segment of the item or t is outside [0, 1]."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        q = np.zeros(len(it), EDGE_QUERY_DTYPE)
+        q["item"] = it
+        q["index"] = np.asarray(indices, dtype=np.uint32)
+        q["t"] = np.asarray(ts, dtype=np.float32)
+        out = np.zeros(len(q), LENGTH_AT_DTYPE)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_positions_on_edges(self._h, q.ctypes.data, len(q), flags, out.ctypes.data), "pm_positions_on_edges")
+        return out
+
+    def positions_on_edges_tensor(self, queries, out, stream=None, skip_transparent: bool = False) -> None:
+        """The same on torch CUDA tensors, asynchronous: queries int32 [n, 4] (the 16-byte EDGE_QUERY_DTYPE records {item, index, t's
+        bits, 0} -- columns 0, 2 and 3 of what snap_tensor wrote and a column of zeros), out int32 [n, 4]
+        (out.cpu().numpy().view(LENGTH_AT_DTYPE)), both contiguous.  `stream` as in hit_test_tensor."""
+        if not (queries.is_cuda and out.is_cuda) or str(queries.dtype) != "torch.int32" or queries.dim() != 2 or queries.shape[1] != 4 or not queries.is_contiguous():
+            raise TypeError("positions_on_edges_tensor needs a contiguous CUDA int32 tensor [n, 4]")
+        n = queries.shape[0]
+        if str(out.dtype) != "torch.int32" or tuple(out.shape) != (n, 4) or not out.is_contiguous():
+            raise TypeError("positions_on_edges_tensor writes a contiguous CUDA int32 tensor [n, 4]")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_positions_on_edges_device(self._h, queries.data_ptr(), n, flags, out.data_ptr(), s), "pm_positions_on_edges_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def path_lengths(self, skip_transparent: bool = False):
+        """(lengths, n_items) per path of the PathSet: the sum of item_lengths over the items each path produced (item_paths), in
+        units of 2^-16 px as Python integers, and how many items that is.  Needs a scene made by flatten_and_encode / reflatten."""
+        of_item = self.item_paths()
+        rec = self.item_lengths(skip_transparent)
+        n_paths = int(of_item.max()) + 1 if len(of_item) else 0
+        lengths, counts = [0] * n_paths, [0] * n_paths
+        for p, v in zip(of_item.tolist(), rec["length"].tolist()):
+            lengths[p] += int(v)
+            counts[p] += 1
+        return lengths, counts
 
     def item_paths(self) -> np.ndarray:
         """For a scene made by flatten_and_encode / reflatten: the index of the path (into the PathSet) that produced each item."""
