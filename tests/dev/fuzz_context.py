@@ -4,7 +4,9 @@ prints the step, and -- for a comparison that failed, not for an error of the ru
 greedily while the same kind of failure persists and the script stays one the model allows.  On a box without a GPU it runs on the
 wave64 emulation of the kernels (where a host bug reproduces; a missing wait does not).
 
-    python tests/dev/fuzz_context.py [first_seed] [count] [--changes N] [--seconds S]
+    python tests/dev/fuzz_context.py [first_seed] [count] [--changes N] [--seconds S] [--queries]
+
+--queries: walk with tests/context_queries.QueryRunner -- the seven newer query families behind every state change and in flight.
 """
 import argparse
 import os
@@ -17,6 +19,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import piet_metal_amd as pm  # noqa: E402
 from oracle import pmo  # noqa: E402
 import context_model as cm  # noqa: E402
+import context_queries as cq  # noqa: E402
+
+RUNNER = [cm.Runner]
 
 
 def allowed(script):
@@ -41,7 +46,7 @@ def failure(script, seed, answers):
     """None, or the AssertionError of the script on a fresh Renderer."""
     with pm.Renderer(0) as r:
         try:
-            cm.Runner(pm, pmo, r, script, seed, answers=answers).run()
+            RUNNER[0](pm, pmo, r, script, seed, answers=answers).run()
         except AssertionError as e:
             return e
     return None
@@ -72,7 +77,11 @@ def main():
     ap.add_argument("count", nargs="?", type=int, default=50)
     ap.add_argument("--changes", type=int, default=25, help="state changes per script (the committed scripts have 11)")
     ap.add_argument("--seconds", type=float, default=0.0, help="start no script after this much wall time (0: no limit)")
+    ap.add_argument("--queries", action="store_true", help="walk with QueryRunner: the newer query families too")
     args = ap.parse_args()
+    if args.queries:
+        answers2 = cq.Answers2()
+        RUNNER[0] = lambda *a, **kw: cq.QueryRunner(*a, answers2=answers2, **kw)
     import torch
 
     if not torch.cuda.is_available():
@@ -101,6 +110,8 @@ def main():
         steps += len(script)
         if len(answers.cache) > 4000:
             answers.cache.clear()
+        if args.queries and len(answers2.cache) > 4000:
+            answers2.cache.clear()
         print(f"seed {seed}: {len(script)} steps, {time.time() - t0:.1f} s", flush=True)
     print(f"context fuzz: {done} scripts ({steps} steps, {args.changes} state changes each) from seed {args.first}: no failure, {time.time() - t0:.1f} s")
     return 0

@@ -1,6 +1,8 @@
 """The host-memory query calls share ONE grow-only staging buffer on the device (QueryStaging, piet_metal_amd/csrc/pm_context.hip):
-pm_hit_test, pm_hit_frame, pm_hit_rects, pm_select_rect, pm_select_polygon, pm_snap, pm_snap_intersections, pm_item_bounds and
-pm_union_bounds lay their records, their queries and their per-item words out in it, each in its own way, and every such call ends
+pm_hit_test, pm_hit_frame, pm_hit_rects, pm_select_rect, pm_select_polygon, pm_snap, pm_snap_intersections, pm_item_bounds,
+pm_union_bounds, pm_hit_stack, pm_hit_rects_stack, pm_item_lengths, pm_points_at_length and pm_positions_on_edges lay their
+records, their queries and their per-item words out in it, each in its own way (the stacks: k words and a count per query in front
+of the queries; the measure calls: 16-byte queries behind 32- or 16-byte records, or a record per item), and every such call ends
 with the context's stream synchronised.  What one call leaves in the buffer, and whether the buffer grew or was reused, must not
 show in the next call's answer.
 
@@ -20,6 +22,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import np_cross  # noqa: E402
 import np_hit  # noqa: E402
+from np_measure import ITEM_LENGTH, LENGTH_POINT  # noqa: E402
 import np_snap  # noqa: E402
 import snap_cases as sc  # noqa: E402
 from test_snap import as_rec, device_snap, same  # noqa: E402
@@ -49,12 +52,28 @@ def _rects(n, seed):
     return np.concatenate([p - t, p + t], axis=1).astype(np.float32)
 
 
+STACK_K = 7
+
+
+def _items(case, n):
+    """n item indices: over the scene's items and one past the last."""
+    return (np.arange(n, dtype=np.uint32) * 7) % np.uint32(len(case.mask) + 1)
+
+
+def _positions(n):
+    """n positions in units of 2^-16 px: 0, then steps of 3.25 px, so that ends, interiors and positions beyond the end occur."""
+    return (np.arange(n, dtype=np.uint64) % 97) * np.uint64(212992)
+
+
 def _bytes(*arrays):
     return b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)
 
 
 # family -> call(renderer, case, n) -> the answer as bytes, in the order of the calls.  select_rect, select_polygon and item_bounds
 # have no number of queries: they stage a word or a record per item.  union_bounds stages n records and two words per item.
+# The five calls of D24 and D25 stand at the end, so that the first ten calls of schedule() and their sizes are what they were:
+# the stacks stage n * (k + 1) words and the queries (k = 7: records of no power of two), item_lengths a record per item, the two
+# per-query measure calls n records and n queries (items cycle over the scene and one past it, positions over a few lengths).
 FAMILIES = {
     "hit_test": lambda r, case, n: _bytes(*r.hit_test(_points(n, 11), counts=True)),
     "hit_rects": lambda r, case, n: _bytes(*r.hit_rects(_rects(n, 12), counts=True)),
@@ -66,6 +85,11 @@ FAMILIES = {
     "snap_intersections": lambda r, case, n: _bytes(r.snap_intersections(_points(n, 16), _radii(n, 17))),
     "item_bounds": lambda r, case, n: _bytes(r.item_bounds()),
     "union_bounds": lambda r, case, n: _bytes(r.union_bounds(np.arange(len(case.mask), dtype=np.uint32) % n, n, item_flags=case.mask == 0, mask=1)),
+    "item_lengths": lambda r, case, n: _bytes(r.item_lengths()),
+    "hit_stack": lambda r, case, n: _bytes(*r.hit_stack(_points(n, 18), STACK_K, counts=True)),
+    "hit_rects_stack": lambda r, case, n: _bytes(*r.hit_rects_stack(_rects(n, 19), STACK_K, stop_at_opaque=True, counts=True)),
+    "points_at_length": lambda r, case, n: _bytes(r.points_at_units(_items(case, n), _positions(n))),
+    "positions_on_edges": lambda r, case, n: _bytes(r.positions_on_edges(_items(case, n), np.arange(n) % 5, (np.arange(n) % 9) / np.float32(8.0))),
 }
 
 
@@ -113,6 +137,15 @@ def test_interleaved_host_calls_answer_as_on_a_fresh_context(pm):
     assert fresh["snap_masked"] == np_snap.snap(case.scene, xyr, skip_items=case.mask).tobytes() != np_snap.snap(case.scene, xyr).tobytes()
     assert len(fresh["union_bounds"]) == sizes["union_bounds"] * 40 and len(fresh["item_bounds"]) == len(case.mask) * 32
     assert np.frombuffer(fresh["select_polygon"], np.bool_).any() and np.frombuffer(fresh["select_rect"], np.bool_).any()
+    n = sizes["hit_stack"]
+    assert len(fresh["hit_stack"]) == n * (STACK_K + 1) * 4 and len(fresh["hit_rects_stack"]) == sizes["hit_rects_stack"] * (STACK_K + 1) * 4
+    items, cnt = np.frombuffer(fresh["hit_stack"], np.uint32)[:n * STACK_K].reshape(n, STACK_K), np.frombuffer(fresh["hit_stack"], np.uint32)[n * STACK_K:]
+    assert (cnt == 0).any() and (cnt > 1).any() and ((items != NONE).sum(axis=1) == np.minimum(cnt, STACK_K)).all()
+    lengths = np.frombuffer(fresh["item_lengths"], ITEM_LENGTH)
+    assert len(lengths) == len(case.mask) and (lengths["length"] > 0).any()
+    pts = np.frombuffer(fresh["points_at_length"], LENGTH_POINT)
+    assert len(pts) == sizes["points_at_length"] and (pts["item"] != NONE).any() and (pts["item"] == NONE).any() and len(set(pts["status"].tolist())) > 2
+    assert len(fresh["positions_on_edges"]) == sizes["positions_on_edges"] * 16
 
 
 @pytest.mark.gpu
