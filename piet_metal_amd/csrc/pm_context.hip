@@ -34,6 +34,8 @@
 
 #include "../../include/piet_metal_amd.h"
 #include "pm_device.h"
+#include "pm_dev_array.h"
+#include "pm_plan.h"
 #include "pm_flatten.h"
 #include "pm_hit_test.h"  // pm_hit_kernel + LaunchHitTest: point hit testing
 #include "pm_hit_frame.h"  // pm_hit_frame_kernel + LaunchHitFrame: the item map, a workgroup per 16 x 16 tile
@@ -165,8 +167,7 @@ struct FrameSlot {
     uint32_t *d_tile_state = nullptr;
     uint32_t *d_tile_ptcl = nullptr;
     uint32_t *d_tile_ncmd = nullptr;
-    uint4 *d_ptcl = nullptr;  // tile arena: per-tile pieces + command lists
-    uint32_t ptcl_cap = 0;    // quads (16 B)
+    pm::DevArray<uint4> ptcl;  // tile arena: per-tile pieces + command lists, in quads (16 B; never more than 2^31 of them)
     uint2 *d_row_bbox = nullptr;  // per-tile-row item lists of this slot's frame (large scenes)
     uint32_t *d_row_item = nullptr;
     uint64_t row_cap = 0;         // entries allocated for them
@@ -205,10 +206,7 @@ struct pm_ctx {
     uint32_t dense_factor = 4;  // PM_DENSE_FACTOR: a frame whose long lists x this would fill every wave renders each tile with one wave
     uint32_t heavy_stream = 72, heavy_stream_lone = 40, vheavy_stream = 112;  // list-length classes (PM_HEAVY_STREAM / PM_VHEAVY_STREAM)
     uint32_t bin_waves_env = 0;     // PM_BIN_WAVES: 4 / 1 waves per strip row in pm_bin_kernel (0: by the number of strip rows, EnsureArena)
-    uint32_t bin_waves = 4;
     uint32_t bin_waves_inflight = 1;  // PM_BIN_WAVES_INFLIGHT: waves per strip row for frames submitted behind frames still running (1 / 4)
-    uint64_t row_want = 0;          // entries of a slot's per-tile-row item lists (use_row_lists)
-    uint64_t plan_cands = 0;        // (item, strip row) pairs of the plan in force: candidates the strip rows will look at
     uint32_t bin_wg_per_cu = 0xff;  // pm_bin_kernel's workgroups per CU (PM_BIN_WG_PER_CU; 0 = one per strip row, default: by the number of strip rows)
     uint32_t coarse_wg_per_cu = 5, fine_wg_per_cu = 5;  // persistent grids (PM_COARSE_WG_PER_CU, PM_FINE_WG_PER_CU)
     uint32_t fine_wg_per_cu_inflight = 3;               // ... of a frame behind other frames (PM_FINE_WG_PER_CU_INFLIGHT)
@@ -224,14 +222,8 @@ struct pm_ctx {
     bool one_launch_broken = false;   // a frame gave up waiting inside the launch (pm_sync rendered it again): two launches from then on
     uint32_t frame_wg_per_cu = 0;     // resident workgroups of pm_frame_kernel per CU (0: cannot run five, one-launch frames are off)
     uint32_t frame_spin_ticks = 200000;  // PM_ONE_LAUNCH_SPIN_US x 100: a wait inside the launch gives up after this long
-    uint32_t *d_sr_next_one = nullptr;  // [n_sr_active] chains of the one-launch grid (0: the workgroup's last strip row)
-    size_t sr_next_one_cap = 0;
-    uint32_t one_grid_rows = 0;       // binning workgroups of a one-launch frame (0: its strip rows do not fit two per workgroup)
-    std::vector<uint32_t> stage_next_one;
-    uint32_t *d_idle_sr = nullptr;    // strip rows of the band no item reaches (the launch writes their pixels too)
-    size_t idle_sr_cap = 0;
-    uint32_t n_idle_sr = 0;
-    std::vector<uint32_t> stage_idle;
+    pm::DevArray<uint32_t> sr_next_one;  // [work list] chains of the one-launch grid (0: the workgroup's last strip row)
+    pm::DevArray<uint32_t> idle_sr;      // strip rows of the band no item reaches (the launch writes their pixels too)
     uint32_t frames_one_launch = 0;   // frames submitted as one launch (pm_one_launch_info)
     // pm_debug_capture_ptcl of a one-launch frame: the frame is rendered once more with the capture instantiation of its kernel
     uint32_t *cap_counts = nullptr, *cap_solid = nullptr;
@@ -257,12 +249,6 @@ struct pm_ctx {
     std::vector<uint8_t> item_meta;
     bool meta_colours_stale = false;
     std::vector<uint32_t> chunk_base_host;  // source of the asynchronous upload of the chunk table
-    std::vector<uint64_t> stage_need_diff;  // StripRowBounds' scratch
-    std::vector<uint4> stage_desc;          // ... of the strip-row work list,
-    std::vector<uint2> stage_list;          // ... its rows' item lists,
-    std::vector<uint2> stage_bbs;           // ... the band's item boxes
-    std::vector<uint32_t> stage_ids, stage_rb;  // ... and indices, the per-row list offsets
-    size_t row_base_cap = 0;
     uint32_t *d_chunk_base = nullptr;  // scene index: first chunk of every item (+ total)
     float4 *d_chunk_bbox = nullptr;    // scene index: bounding box of every chunk of segments
     float4 *d_sup_bbox = nullptr;      // ... and of every super-chunk (kSuperChunks consecutive chunk-table entries)
@@ -277,11 +263,13 @@ struct pm_ctx {
     uint32_t vp_epoch = 1;  // bumped by every resize / band change
 
     // binning state shared by the slots
-    size_t sr_desc_cap = 0, band_cap = 0;
-    uint4 *d_sr_desc = nullptr;     // strip rows some item reaches: {strip row, arena region begin, end, next of the chain}
-    uint2 *d_sr_list = nullptr;     // ... and, for large scenes, where their tile row's item list is
-    uint32_t n_sr_active = 0;
-    uint32_t bin_grid = 1;          // workgroups of pm_bin_kernel (each walks a chain of strip rows)
+    // The plan in force (pm_plan.h: strip-row work list, arena regions, band list, the item boxes it was made for) -- its vectors are
+    // the sources of the asynchronous uploads -- and its lists on the device (grow only).  A view change (pm_reflatten) plans with
+    // every box widened by a tile, so that the scenes that follow can keep the plan while their boxes stay inside the widened ones
+    // and their items keep their segment counts: no host sizing, no uploads, no waits (0.04 of an animated frame's 0.18 ms).
+    pm::BinPlan plan;
+    pm::DevArray<uint4> sr_desc;    // strip rows some item reaches: {strip row, arena region begin, end, next of the chain}
+    pm::DevArray<uint2> sr_list;    // ... and, for large scenes, where their tile row's item list is
     uint32_t bin_prio_slots = 1024; // PM_BIN_PRIO_SLOTS
     // Heavy strip rows cut in two (round 6): binning ends with its heaviest strip rows (a 4K Tiger frame: 1 109 rows, the mean one
     // through at 15 us, the heaviest at 24), and a row's length is dependent steps of its four waves, so the heaviest rows get EIGHT:
@@ -294,37 +282,21 @@ struct pm_ctx {
                                           // candidates predict a row's segment slots poorly: of the 4K Tiger's 60 heaviest rows they name 32)
     uint32_t bin_split_slots = 224;  // PM_BIN_SPLIT_SLOTS: ... with at least this many segment slots, once frames have reported
     uint32_t bin_split_fill = 15;    // PM_BIN_SPLIT_FILL: cut rows while the work list stays within this many sixteenths of the resident grid
-    uint32_t n_sr_split = 0;         // strip rows of the plan in force that are cut in two
-    uint4 *d_sr_desc_whole = nullptr;  // [sr_desc_cap] the same work list with every cut strip row whole again (same arena regions): what frames
-    uint32_t n_sr_whole = 0;           // behind running frames bin from -- there instructions count, not the frame's own latency (sustained -3 % with cuts)
-    std::vector<uint4> stage_desc_whole;
-    uint32_t *d_sr_slots = nullptr;  // [sr_desc_cap] segment slots every entry of the work list found in the latest frame
+    pm::DevArray<uint4> sr_desc_whole;  // the same work list with every cut strip row whole again (same arena regions): what frames behind
+                                        // running frames bin from -- there instructions count, not the frame's own latency (sustained -3 % with cuts)
+    pm::DevArray<uint32_t> sr_slots;  // segment slots every entry of the work list found in the latest frame
     std::vector<uint32_t> fb_slots;  // per strip row of the band: the slots the frames of this scene and viewport reported (empty: nothing yet)
     std::vector<uint32_t> stage_slots;
     uint32_t frames_on_plan = 0;     // frames submitted since the plan in force was made
-    bool fb_applied = false;         // the plan in force was made with fb_slots
     uint32_t plans_fed_back = 0;     // plans remade from the frames' report (pm_binning_info)
-    uint32_t sr_empty_dwords = 0;   // size of a region no item reaches
-    uint2 *d_band_bbox = nullptr;   // items that reach the band (bbox, scene index), paint order
-    uint32_t *d_band_item = nullptr;
-    uint32_t n_band_items = 0;
-    uint32_t *d_row_base = nullptr;  // per-tile-row item lists (large scenes): offsets
+    pm::DevArray<uint2> band_bbox;  // items that reach the band (bbox, scene index), paint order
+    pm::DevArray<uint32_t> band_item;
+    pm::DevArray<uint32_t> row_base;  // per-tile-row item lists (large scenes): offsets
     uint32_t frames_bin_wave = 0, frames_bin_wave_inflight = 0, frames_bin_no_chains = 0;  // pm_binning_info
-    uint32_t row_total = 0;
-    uint32_t row_parts = 1, row_part_items = pm::kRowCullStep;  // pm_rowcull_kernel's workgroups per tile row and their share of the items
-    bool use_row_lists = false;
     uint32_t arena_cap = 0;         // dwords per slot
     uint64_t ptcl_want = 0;         // commands a slot's list arena starts with / was grown to
     bool arena_dirty = true;
-    // The plan in force (strip-row work list, arena regions, band list) and the item boxes it was made for.  A view change
-    // (pm_reflatten) plans with every box widened by a tile, so that the scenes that follow can keep the plan while their boxes
-    // stay inside the widened ones and their items keep their segment counts: no host sizing, no uploads, no waits
-    // (0.04 of an animated frame's 0.18 ms).
-    std::vector<uint16_t> plan_box;   // [4 n] widened boxes
-    std::vector<uint32_t> plan_per;   // [n] arena dwords per item
-    bool plan_reusable = false;       // the plan was made with widened boxes, for the whole item list in scene order, without per-row lists
     bool replan_wide = false;         // the next plan widens the boxes (set by pm_reflatten)
-    bool band_identity = false;       // the band's item list IS the scene's item list: the kernels read the scene's own boxes
     uint32_t arena_epoch = 0;       // bumped whenever the set of strip rows without a workgroup changes (EnsureArena)
 
     std::vector<FrameSlot> slot;
@@ -483,9 +455,9 @@ int AllocViewport(pm_ctx *c) {
     const int r0 = AllocSlotViewport(c, &c->slot[0]);
     if (r0 != PM_OK) return r0;
     c->arena_dirty = true;
-    c->plan_reusable = false;  // (another viewport or band: the plan goes with it)
+    c->plan.reusable = false;  // (another viewport or band: the plan goes with it)
     c->fb_slots.clear();       // (... and what its frames said about its strip rows)
-    c->fb_applied = false;
+    c->plan.fb_applied = false;
     return PM_OK;
 }
 
@@ -536,484 +508,116 @@ int EnsureSlotBuffers(pm_ctx *c, FrameSlot *s) {
         PM_TRY(hipMalloc(&s->d_arena, static_cast<size_t>(std::max<uint32_t>(c->arena_cap, pm::kArenaBase)) * sizeof(uint32_t)));
         s->arena_cap = c->arena_cap;
     }
-    if (c->use_row_lists && (!s->d_row_bbox || s->row_cap < c->row_want)) {
+    if (c->plan.use_row_lists && (!s->d_row_bbox || s->row_cap < c->plan.row_want)) {
         // per-tile-row item lists of this slot's frames (pm_rowcull_kernel writes them): boxes, then indices, ONE allocation
         if (s->d_row_bbox) (void)hipFree(s->d_row_bbox);
         s->d_row_bbox = nullptr;
         s->d_row_item = nullptr;
         s->row_cap = 0;
-        const uint64_t cap = c->row_want + c->row_want / 4;
+        const uint64_t cap = c->plan.row_want + c->plan.row_want / 4;
         PM_TRY(hipMalloc(&s->d_row_bbox, cap * (sizeof(uint2) + sizeof(uint32_t))));
         s->d_row_item = reinterpret_cast<uint32_t *>(s->d_row_bbox + cap);
         s->row_cap = cap;
     }
-    if (!s->d_ptcl || s->ptcl_cap < c->ptcl_want) {
-        if (s->d_ptcl) (void)hipFree(s->d_ptcl);
-        s->d_ptcl = nullptr;
-        s->ptcl_cap = 0;
-        const uint64_t quads = std::max<uint64_t>(c->ptcl_want, 64);
-        PM_TRY(hipMalloc(&s->d_ptcl, quads * sizeof(uint4)));
-        s->ptcl_cap = static_cast<uint32_t>(quads);
-    }
+    PM_TRY(s->ptcl.Reserve(c->ptcl_want, std::max<uint64_t>(c->ptcl_want, 64)));
     return PM_OK;
 }
 
-// Worst-case binning-arena demand of every strip row of the band (dwords): every candidate item
-// costs kChunkSegs segment slots (16 B) + meta words per chunk (every chunk surviving), plus a token
-// amount that tells a strip row some item reaches from one nothing reaches.  The binning kernel
-// bump-allocates inside these private regions, so the bound must be exact or larger.
-// (need_half, cnt: optional -- the same bound for the two halves of every strip row [2 i], [2 i + 1] (tiles 0-7, 8-15), and the
-//  candidates of every strip row: what EnsureArena cuts heavy strip rows in two with)
-void StripRowBounds(pm_ctx *c, std::vector<uint64_t> *need, int margin, std::vector<uint64_t> *need_half = nullptr, std::vector<uint32_t> *cnt = nullptr) {
-    const uint8_t *meta = c->item_meta.data();
-    uint32_t n, items_ix;
-    std::memcpy(&n, meta, 4);
-    std::memcpy(&items_ix, meta + 4, 4);
-    const uint32_t rows = BandRows(c);
-    need->assign(static_cast<size_t>(rows) * c->strips_x, 0);
-    const size_t w = static_cast<size_t>(c->strips_x) + 1;
-    std::vector<uint64_t> &diff = c->stage_need_diff;
-    diff.assign((static_cast<size_t>(rows) + 1) * w, 0);
-    const size_t wh = 2 * static_cast<size_t>(c->strips_x) + 1;
-    std::vector<uint64_t> diff_half;
-    std::vector<int64_t> diff_cnt;
-    if (need_half) diff_half.assign((static_cast<size_t>(rows) + 1) * wh, 0);
-    if (cnt) diff_cnt.assign((static_cast<size_t>(rows) + 1) * w, 0);
-    c->plan_box.resize(4ull * n);
-    c->plan_per.resize(n);
-    c->plan_cands = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        uint16_t bb[4];
-        std::memcpy(bb, meta + 8 + 8ull * i, 8);
-        // (the box the plan is made for: the item's own, or widened by `margin` pixels on every side)
-        bb[0] = static_cast<uint16_t>(std::max(0, static_cast<int>(bb[0]) - margin));
-        bb[1] = static_cast<uint16_t>(std::max(0, static_cast<int>(bb[1]) - margin));
-        bb[2] = static_cast<uint16_t>(std::min(65535, static_cast<int>(bb[2]) + margin));
-        bb[3] = static_cast<uint16_t>(std::min(65535, static_cast<int>(bb[3]) + margin));
-        std::memcpy(&c->plan_box[4ull * i], bb, 8);
-        const uint8_t *it = meta + items_ix + 32ull * i;
-        uint32_t tag, npt = 0;
-        std::memcpy(&tag, it, 4);
-        tag &= 0xffffu;
-        std::memcpy(&npt, it + 12, 4);
-        uint64_t nseg = 0;
-        if (tag == pm::kItemFill) nseg = npt;
-        if (tag == pm::kItemPoly && npt >= 2) nseg = npt - 1;
-        if (tag == pm::kItemLine) nseg = 1;
-        if (margin > 0 && tag != pm::kItemLine) nseg += nseg / 4 + 2 * pm::kChunkSegs;  // (a zooming view: curves flatten into more segments as they grow)
-        const uint64_t nch = (nseg + pm::kChunkSegs - 1) / pm::kChunkSegs;
-        const uint64_t per = 4u + static_cast<uint64_t>(pm::kSlotDwords) * pm::kChunkSegs * nch;
-        c->plan_per[i] = static_cast<uint32_t>(std::min<uint64_t>(per, 0xffffffffull));
-        // strips: bz >= sx0 && bx < sx0 + 256 ; rows: bw >= y0 && by < y0 + 16
-        const int64_t s_lo = bb[0] / 256, s_hi = std::min<int64_t>(bb[2] / 256, static_cast<int64_t>(c->strips_x) - 1);
-        const int64_t r_lo = std::max<int64_t>(bb[1] / 16, c->row0), r_hi = std::min<int64_t>(bb[3] / 16, static_cast<int64_t>(c->row1) - 1);
-        if (r_lo > r_hi || s_lo > s_hi) continue;
-        c->plan_cands += static_cast<uint64_t>(r_hi - r_lo + 1) * static_cast<uint64_t>(s_hi - s_lo + 1);
-        // (a 2-D difference array: four updates per item instead of one per strip row it covers -- config 5's
-        //  7 600 items cover millions of them: arena sizing 0.26 -> 0.10 ms)
-        const size_t a = static_cast<size_t>(r_lo - c->row0), b = static_cast<size_t>(r_hi - c->row0) + 1;
-        diff[a * w + static_cast<size_t>(s_lo)] += per;
-        diff[a * w + static_cast<size_t>(s_hi) + 1] -= per;
-        diff[b * w + static_cast<size_t>(s_lo)] -= per;
-        diff[b * w + static_cast<size_t>(s_hi) + 1] += per;
-        if (cnt) {
-            diff_cnt[a * w + static_cast<size_t>(s_lo)] += 1;
-            diff_cnt[a * w + static_cast<size_t>(s_hi) + 1] -= 1;
-            diff_cnt[b * w + static_cast<size_t>(s_lo)] -= 1;
-            diff_cnt[b * w + static_cast<size_t>(s_hi) + 1] += 1;
-        }
-        if (need_half) {  // half strips: bz >= hx0 && bx < hx0 + 128
-            const size_t h_lo = bb[0] / 128, h_hi = std::min<size_t>(bb[2] / 128, 2 * static_cast<size_t>(c->strips_x) - 1);
-            diff_half[a * wh + h_lo] += per;
-            diff_half[a * wh + h_hi + 1] -= per;
-            diff_half[b * wh + h_lo] -= per;
-            diff_half[b * wh + h_hi + 1] += per;
-        }
-    }
-    if (cnt) {
-        cnt->assign(static_cast<size_t>(rows) * c->strips_x, 0);
-        for (size_t r = 0; r < rows; ++r) {
-            int64_t run = 0;
-            for (size_t sx = 0; sx < c->strips_x; ++sx) {
-                run += diff_cnt[r * w + sx];
-                (*cnt)[r * c->strips_x + sx] = static_cast<uint32_t>(run + (r ? static_cast<int64_t>((*cnt)[(r - 1) * c->strips_x + sx]) : 0));
-            }
-        }
-    }
-    if (need_half) {
-        const size_t hs = 2 * static_cast<size_t>(c->strips_x);
-        need_half->assign(static_cast<size_t>(rows) * hs, 0);
-        for (size_t r = 0; r < rows; ++r) {
-            uint64_t run = 0;
-            for (size_t hx = 0; hx < hs; ++hx) {
-                run += diff_half[r * wh + hx];
-                (*need_half)[r * hs + hx] = run + (r ? (*need_half)[(r - 1) * hs + hx] : 0);
-            }
-        }
-    }
-    for (size_t r = 0; r < rows; ++r) {  // prefix sums along the strips, then down the rows (mod 2^64: the totals are exact)
-        uint64_t run = 0;
-        for (size_t sx = 0; sx < c->strips_x; ++sx) {
-            run += diff[r * w + sx];
-            (*need)[r * c->strips_x + sx] = run + (r ? (*need)[(r - 1) * c->strips_x + sx] : 0);
-        }
-    }
+// A list of the plan on its way to the device: asynchronous, on the context's stream, read from the plan's own vector.
+template <typename T>
+hipError_t UploadList(pm_ctx *c, T *dst, const std::vector<T> &src) {
+    if (src.empty()) return hipSuccess;
+    return hipMemcpyAsync(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice, c->stream);
 }
 
+// The binning plan of the resident scene, viewport and band (pm_plan.h), made when something it depends on changed, and its lists
+// on the device: the reuse check, the planner, a wait for the frames in flight, the device lists grown and filled, one stream wait.
 int EnsureArena(pm_ctx *c) {
     if (!c->arena_dirty && c->arena_cap != 0) return PM_OK;
     if (c->item_meta.empty() || c->tiles_x == 0) return PM_OK;  // nothing to size against yet
     const WallTimer timer;
-    {
-        // Does the plan in force still hold?  Same items in the same order, every item with the arena need it was planned with
-        // and its box inside the (widened) box it was planned with.
-        const uint8_t *meta = c->item_meta.data();
-        uint32_t n, items_ix;
-        std::memcpy(&n, meta, 4);
-        std::memcpy(&items_ix, meta + 4, 4);
-        bool ok = c->plan_reusable && c->arena_cap != 0 && c->band_identity && n == c->plan_per.size() && n == c->n_band_items;
-        for (uint32_t i = 0; i < n && ok; ++i) {
-            uint16_t bb[4];
-            std::memcpy(bb, meta + 8 + 8ull * i, 8);
-            const uint16_t *pb = &c->plan_box[4ull * i];
-            const uint8_t *it = meta + items_ix + 32ull * i;
-            uint32_t tag, npt = 0;
-            std::memcpy(&tag, it, 4);
-            tag &= 0xffffu;
-            std::memcpy(&npt, it + 12, 4);
-            uint64_t nseg = 0;
-            if (tag == pm::kItemFill) nseg = npt;
-            if (tag == pm::kItemPoly && npt >= 2) nseg = npt - 1;
-            if (tag == pm::kItemLine) nseg = 1;
-            const uint64_t per = 4u + static_cast<uint64_t>(pm::kSlotDwords) * pm::kChunkSegs * ((nseg + pm::kChunkSegs - 1) / pm::kChunkSegs);
-            ok = per <= c->plan_per[i] && bb[0] >= pb[0] && bb[1] >= pb[1] && bb[2] <= pb[2] && bb[3] <= pb[3] && bb[2] >= bb[0] && bb[3] >= bb[1];
-        }
-        if (ok) {
-            // (the scene index of the new scene is still being built on the context's stream; frames run on the others)
-            PM_TRY(hipStreamSynchronize(c->stream));
-            c->arena_dirty = false;
-            c->t_arena_ms = timer.ms();
-            return PM_OK;
-        }
+    pm::BinPlan &plan = c->plan;
+    pm::PlanInput in;
+    in.item_meta = c->item_meta.data();
+    in.n_items = c->n_items;
+    in.n_chunks = c->n_chunks;
+    in.tiles_x = c->tiles_x;
+    in.strips_x = c->strips_x;
+    in.row0 = c->row0;
+    in.row1 = c->row1;
+    in.n_cus = c->n_cus;
+    in.margin = c->replan_wide ? static_cast<int>(pm::kTileW) : 0;
+    in.bin_split_mode = c->bin_split_mode;
+    in.bin_split_cands = c->bin_split_cands;
+    in.bin_split_slots = c->bin_split_slots;
+    in.bin_split_fill = c->bin_split_fill;
+    in.bin_wg_per_cu = c->bin_wg_per_cu;
+    in.bin_waves_env = c->bin_waves_env;
+    in.bin_waves_inflight = c->bin_waves_inflight;
+    in.one_launch_mode = c->one_launch_mode;
+    in.frame_wg_per_cu = c->frame_wg_per_cu;
+    in.fold_clear_mode = c->fold_clear_mode;
+    in.fb_slots = c->fb_slots.data();
+    in.n_fb_slots = c->fb_slots.size();
+    in.arena_cap = c->arena_cap;
+    in.ptcl_want = c->ptcl_want;
+    if (pm::PlanStillHolds(in, plan)) {
+        // (the scene index of the new scene is still being built on the context's stream; frames run on the others)
+        PM_TRY(hipStreamSynchronize(c->stream));
+        c->arena_dirty = false;
+        c->t_arena_ms = timer.ms();
+        return PM_OK;
     }
     // (host work first: the scene-index kernel of a scene replacement is still running on the device)
-    const int margin = c->replan_wide ? static_cast<int>(pm::kTileW) : 0;
-    std::vector<uint64_t> need, need_half;
-    std::vector<uint32_t> row_cands;
-    bool may_split = c->bin_split_mode != 0 && c->one_launch_mode == 0;  // (scenes with per-tile-row item lists: decided below, once the band's list is made)
-    StripRowBounds(c, &need, margin);
-    if (may_split && c->bin_split_mode == 1) {  // (cuts only while the plan's rows leave room in the resident grid: large frames pay for no second sizing pass)
-        size_t n_rows = 0;
-        for (size_t i = 0; i < need.size(); ++i) n_rows += need[i] != 0 ? 1u : 0u;
-        may_split = n_rows < static_cast<size_t>(c->n_cus) * 5u;
+    in.row_list_min_items = EnvInt("PM_ROW_LIST_MIN_ITEMS", 2048, 0, 1 << 30);
+    in.row_list_part_items = EnvInt("PM_ROW_LIST_PART_ITEMS", 0, 1, 1 << 30);  // (the tests cut small scenes into many parts)
+    if (const char *v = std::getenv("PM_PTCL_INITIAL_CMDS"))  // tests: force the overflow -> grow -> re-render path
+        in.ptcl_initial_cmds = std::max<uint64_t>(64, std::strtoull(v, nullptr, 10));
+    if (pm::MakeBinPlan(in, &plan) != PM_OK) {
+        SetError("scene x viewport needs a binning arena beyond 16 GiB");
+        plan = pm::BinPlan();  // (nothing of the failed plan stays: arena_dirty still stands, the next plan is made from scratch)
+        return PM_ERR_CAPACITY;
     }
-    if (may_split) StripRowBounds(c, &need, margin, &need_half, &row_cands);
-    // (host work before any upload: the band's item list, the arena regions)
-    c->sr_empty_dwords = 0;  // (a strip row no item's bbox reaches has nothing reserved)
-    // the items whose bbox reaches the band (rows: bw >= y0 && by < y1, PietRender.metal:198/:214), paint order
-    std::vector<uint2> &bbs = c->stage_bbs;
-    std::vector<uint32_t> &ids = c->stage_ids;
-    {
-        const uint8_t *meta = c->item_meta.data();
-        bbs.clear();
-        ids.clear();
-        const uint32_t y0 = c->row0 * pm::kTileH, y1 = c->row1 * pm::kTileH;
-        for (uint32_t i = 0; i < c->n_items; ++i) {
-            uint32_t w[2];
-            std::memcpy(w, meta + 8 + 8ull * i, 8);
-            const uint16_t *pb = &c->plan_box[4ull * i];  // (the box the plan is made for: widened for a view change)
-            const uint32_t bx = pb[0], by = pb[1], bw = pb[3];
-            if (bw >= y0 && by < y1 && bx < c->strips_x * pm::kGroupW) {
-                bbs.push_back(make_uint2(w[0], w[1]));
-                ids.push_back(i);
-            }
-        }
-        c->n_band_items = static_cast<uint32_t>(ids.size());
-        // every item of the scene, in scene order: the kernels can read the scene's own boxes (nothing to upload, and the
-        // list stays right for the next scene with the same items)
-        const int min_items = EnvInt("PM_ROW_LIST_MIN_ITEMS", 2048, 0, 1 << 30);
-        c->use_row_lists = static_cast<int>(ids.size()) >= min_items && !ids.empty();
-        c->band_identity = ids.size() == c->n_items && !c->use_row_lists;
-    }
-    // The strip rows some item's bbox reaches get a workgroup of pm_bin_kernel each; the others are
-    // background for as long as this scene and viewport last: their tile_state is set to white
-    // once, here.  (An empty list still launches one workgroup: it resets the frame counters.)
-    std::vector<uint4> &desc = c->stage_desc;  // (sources of asynchronous uploads live in the context)
-    desc.clear();
-    uint32_t per_cu = c->bin_wg_per_cu;
-    if (per_cu == 0xffu) per_cu = 5u;
-    // Which strip rows are cut in two (bin_split_mode): the heaviest ones, as many as the resident grid has workgroups to spare.
-    std::vector<uint8_t> cut(need.size(), 0);
-    c->n_sr_split = 0;
-    // (the plan is made with the frames' report whether or not it can cut: a report is read back once per plan at most,
-    //  FeedBackStripRows -- round-6 advisor: scenes with per-tile-row item lists drained the pipeline every third frame)
-    const bool fed = c->fb_slots.size() == need.size();  // (frames of this scene and viewport have reported)
-    c->fb_applied = fed;
-    if (may_split && !c->use_row_lists) {  // (per-tile-row item lists are addressed by entry of the one work list)
-        size_t n_rows = 0;
-        for (size_t i = 0; i < need.size(); ++i) n_rows += ((need[i] + 3u) & ~3ull) != c->sr_empty_dwords ? 1u : 0u;
-        // (not to the last workgroup the chip holds: with all 1 280 places taken -- 171 rows cut at the 4K Tiger -- binning was 1.7 us
-        //  SLOWER than with 1 214; the dispatcher's placement is not perfectly even, and a workgroup that has to wait for a place
-        //  starts when a first one ends)
-        const size_t resident = static_cast<size_t>(c->n_cus) * (per_cu ? per_cu : 5u) * static_cast<size_t>(c->bin_split_fill) / 16u;
-        const size_t room = c->bin_split_mode == 2 ? need.size() : (resident > n_rows ? resident - n_rows : 0u);
-        std::vector<std::pair<uint32_t, uint32_t>> heavy;  // {weight, strip row}
-        for (size_t i = 0; i < need.size() && room != 0; ++i) {
-            if (((need[i] + 3u) & ~3ull) == c->sr_empty_dwords) continue;
-            if (c->bin_split_mode == 2) heavy.emplace_back(row_cands[i], static_cast<uint32_t>(i));
-            else if (fed ? c->fb_slots[i] >= c->bin_split_slots : row_cands[i] >= c->bin_split_cands) heavy.emplace_back(fed ? c->fb_slots[i] : row_cands[i], static_cast<uint32_t>(i));
-        }
-        if (heavy.size() > room) {
-            std::partial_sort(heavy.begin(), heavy.begin() + static_cast<ptrdiff_t>(room), heavy.end(),
-                              [](const std::pair<uint32_t, uint32_t> &a, const std::pair<uint32_t, uint32_t> &b) { return a.first != b.first ? a.first > b.first : a.second < b.second; });
-            heavy.resize(room);
-        }
-        for (const auto &h : heavy) cut[h.second] = 1;
-    }
-    uint64_t total = pm::kArenaBase;  // offset 0 means "no record"
-    constexpr uint32_t kWholeStrip = 15u << 12, kLeftHalf = 7u << 12, kRightHalf = (7u << 12) | (8u << 8);  // tiles - 1 << 12 | first tile << 8
-    auto push = [&](size_t i, uint32_t run, uint64_t need_dwords) -> bool {
-        const uint64_t sz = (need_dwords + 3u) & ~3ull;
-        if (sz == c->sr_empty_dwords) return true;
-        const uint64_t begin = total;
-        total += sz;
-        if (total > 0xfffffff0ull) return false;
-        desc.push_back(make_uint4(static_cast<uint32_t>(i % c->strips_x) | run | (static_cast<uint32_t>(i / c->strips_x) << 16), static_cast<uint32_t>(begin),
-                                  static_cast<uint32_t>(total), 0u));
-        return true;
-    };
-    for (size_t i = 0; i < need.size(); ++i) {
-        bool ok = true;
-        const size_t h = (i / c->strips_x) * 2 * c->strips_x + 2 * (i % c->strips_x);
-        // (a half no item reaches gets no entry -- and nobody would write its pixels: such a row stays whole)
-        if (cut[i] && ((need_half[h] + 3u) & ~3ull) != c->sr_empty_dwords && ((need_half[h + 1] + 3u) & ~3ull) != c->sr_empty_dwords) {
-            ok = push(i, kLeftHalf, need_half[h]) && push(i, kRightHalf, need_half[h + 1]);
-            c->n_sr_split += 1;
-        } else {
-            ok = push(i, kWholeStrip, need[i]);
-        }
-        if (!ok) {
-            SetError("scene x viewport needs a binning arena beyond 16 GiB");
-            return PM_ERR_CAPACITY;
-        }
-    }
-    if (desc.empty()) desc.push_back(make_uint4(kWholeStrip, pm::kArenaBase, pm::kArenaBase, 0u));
-    // (exact for a context's first scene; a quarter of headroom when it has to GROW: an animation's
-    //  demand creeps from frame to frame, and re-allocating four 100 MB arenas costs milliseconds)
-    const uint64_t alloc_dwords = total <= c->arena_cap ? c->arena_cap : (c->arena_cap == 0 ? total : std::min<uint64_t>(0xfffffff0ull, total + total / 4));
-    // (the slots' arenas themselves are allocated when a slot is first used, EnsureSlotBuffers: the
-    //  first frame of a scene pays for one arena, not for four -- hundreds of MB each at 8K)
-    {
-        // Tile arena (per-tile pieces + command lists, 16-byte quads): sized from what binning
-        // actually finds, so there is no static bound; start generously (HBM is 288 GB), in proportion
-        // to EVERY scene that comes (a max: what pm_sync grew it to is kept), and let pm_sync grow it on
-        // overflow.
-        uint64_t cmds = std::max<uint64_t>(1u << 22, 64ull * c->n_chunks * pm::kChunkSegs);
-        if (const char *v = std::getenv("PM_PTCL_INITIAL_CMDS"))  // tests: force the overflow -> grow -> re-render path
-            cmds = std::max<uint64_t>(64, std::strtoull(v, nullptr, 10));
-        // (a frame behind running frames may bin with a wave per strip row, Enqueue: records of 64 candidates instead of 256,
-        //  up to four pieces -- four headers, four times the slack behind the candidates -- where a lone frame leaves one.  The
-        //  arena a plan starts with holds that variant too: a frame that fits alone must not overflow in flight.  Round-4 advisor.)
-        if (c->bin_waves_inflight == 1 && !std::getenv("PM_PTCL_INITIAL_CMDS"))
-            cmds = std::max<uint64_t>(cmds, 80ull * c->n_chunks * pm::kChunkSegs + 4ull * BandTiles(c));
-        c->ptcl_want = std::max<uint64_t>(c->ptcl_want, std::min<uint64_t>(cmds * pm::kCmdQuadsNum / pm::kCmdQuadsDen, 0x7fffffffull));
-    }
-    c->arena_cap = std::max<uint32_t>(c->arena_cap, static_cast<uint32_t>(alloc_dwords));
-    // (strip rows stay in their natural order: heaviest-first was measured 2.5 us slower -- the heavy
-    //  ones then share CUs -- and so was a snake order over CU periods; neighbouring strip rows share
-    //  data and belong together)
-    c->n_sr_active = static_cast<uint32_t>(desc.size());
-    {
-        // pm_bin_kernel's grid is no larger than what the chip holds at once: five workgroups per CU (its LDS
-        // is sized for that).  A group walks a chain of strip rows (desc.w = index of the next one, 0 = none):
-        // row b, b + grid, b + 2 grid ... in natural order -- a grid larger than the residency would start its
-        // last groups when the first END their chains.  Measured and not kept: any permutation of ALL rows, +25 %
-        // (neighbouring strip rows share data); pairing the lightest rows by their arena need, +9 % (the need is
-        // the worst case of the chunk test, not the work); rows DRAWN from counters instead of dealt (a returning
-        // atomic per row, sent off a row ahead): config 5 0.229 -> 0.211 ms with a workgroup per row but config 4
-        // 0.140 -> 0.150, and 0.195 -> 0.207 with a wave per row.
-        const size_t n = desc.size();
-        // A wave per strip row instead of a workgroup when there are several times more strip rows than the chip holds
-        // workgroups AND the rows are light (a record of 64 candidates holds nearly every row's): sixteen one-wave
-        // groups share a CU, no workgroup barriers, a quarter fewer vector and a third fewer scalar instructions per
-        // strip row -- a row takes twice as long, three times as many are in flight.  Config 5 (16 160 rows of 11
-        // candidates): binning 0.229 -> 0.195 ms, sustained +7 %; config 4 (4 096 rows of 108): 0.140 -> 0.162, stays
-        // with workgroups; so does any frame whose rows all fit the chip at once (the 4K Tiger: 25 -> 52 us).
-        const bool many_light_rows = n >= static_cast<size_t>(c->n_cus) * 5u * 3u && c->plan_cands <= 32ull * n;
-        c->bin_waves = c->bin_waves_env == 1 || c->bin_waves_env == 4 ? c->bin_waves_env : (many_light_rows ? 1u : 4u);
-        if (c->bin_waves == 1 && c->bin_wg_per_cu == 0xffu) per_cu = 16u;
-        const size_t grid = per_cu == 0 ? n : std::min<size_t>(n, static_cast<size_t>(c->n_cus) * per_cu);
-        if (n > grid) {
-            for (size_t i = 0; i + grid < n; ++i) desc[i].w = static_cast<uint32_t>(i + grid);
-        }
-        c->bin_grid = static_cast<uint32_t>(grid);
-    }
+    // (the slots' arenas and per-tile-row list buffers themselves are allocated when a slot is next used, EnsureSlotBuffers: the
+    //  first frame of a scene pays for one slot's, not for four -- hundreds of MB each at 8K)
+    c->arena_cap = plan.arena_alloc;
+    c->ptcl_want = plan.ptcl_want;
     PM_TRY(SyncAll(c) == PM_OK ? hipSuccess : hipErrorUnknown);  // frames in flight still read the lists replaced below
-    if (desc.size() > c->sr_desc_cap || !c->d_sr_list || !c->d_sr_slots || !c->d_sr_desc_whole) {  // (grow only: an animation re-sizes every frame)
-        if (c->d_sr_desc) (void)hipFree(c->d_sr_desc);
-        if (c->d_sr_list) (void)hipFree(c->d_sr_list);
-        c->d_sr_desc = nullptr;
-        c->d_sr_list = nullptr;
-        c->sr_desc_cap = 0;
-        const size_t want = std::max<size_t>(desc.size() + desc.size() / 4 + 16, c->sr_desc_cap);
-        PM_TRY(hipMalloc(&c->d_sr_desc, want * sizeof(uint4)));
-        PM_TRY(hipMalloc(&c->d_sr_list, want * sizeof(uint2)));
-        if (c->d_sr_slots) (void)hipFree(c->d_sr_slots);
-        c->d_sr_slots = nullptr;
-        PM_TRY(hipMalloc(&c->d_sr_slots, want * sizeof(uint32_t)));
-        if (c->d_sr_desc_whole) (void)hipFree(c->d_sr_desc_whole);
-        c->d_sr_desc_whole = nullptr;
-        PM_TRY(hipMalloc(&c->d_sr_desc_whole, want * sizeof(uint4)));
-        c->sr_desc_cap = want;
+    const size_t n = plan.desc.size();  // (grow only: an animation re-sizes every frame)
+    PM_TRY(c->sr_desc.Reserve(n));
+    PM_TRY(c->sr_list.Reserve(n));
+    PM_TRY(c->sr_slots.Reserve(n));
+    PM_TRY(c->sr_desc_whole.Reserve(n));
+    if (c->one_launch_mode != 0) PM_TRY(c->sr_next_one.Reserve(n));  // (only a context that renders one-launch frames pays for the table)
+    PM_TRY(c->band_bbox.Reserve(plan.band_item.size()));
+    PM_TRY(c->band_item.Reserve(plan.band_item.size()));
+    PM_TRY(hipMemsetAsync(c->sr_slots.p, 0, n * sizeof(uint32_t), c->stream));
+    PM_TRY(UploadList(c, c->sr_desc.p, plan.desc));
+    if (!plan.band_identity) {
+        PM_TRY(UploadList(c, c->band_bbox.p, plan.band_bbox));
+        PM_TRY(UploadList(c, c->band_item.p, plan.band_item));
     }
-    {
-        // the work list without the cuts: the two halves of a cut strip row lie next to each other, in the list and in the arena
-        std::vector<uint4> &whole = c->stage_desc_whole;
-        whole.clear();
-        for (size_t k = 0; k < desc.size() && c->n_sr_split != 0; ++k) {
-            const uint32_t key = desc[k].x & 0xffff00ffu;
-            if (!whole.empty() && (whole.back().x & 0xffff00ffu) == key) whole.back().z = desc[k].z;
-            else whole.push_back(make_uint4(key | (15u << 12), desc[k].y, desc[k].z, 0u));
-        }
-        // (chained for the plan's grid like the list with the cuts: frames that bind this list run min(grid, rows) groups, Enqueue,
-        //  and with more rows than the grid -- PM_BIN_SPLIT=2, or PM_BIN_WG_PER_CU=1 at 1080p -- a row past the grid is reached by
-        //  its chain only.  Round-6 advisor: unchained, those rows were never binned and their tiles stayed unrendered.)
-        for (size_t k = 0; k + c->bin_grid < whole.size(); ++k) whole[k].w = static_cast<uint32_t>(k + c->bin_grid);
-        c->n_sr_whole = static_cast<uint32_t>(whole.size());
-        if (!whole.empty()) PM_TRY(hipMemcpyAsync(c->d_sr_desc_whole, whole.data(), whole.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
+    // The rest of the plan, made while the uploads above are under way.  (Its failure is out of reach through this call -- per-row
+    // lists that long come with an arena beyond its limit, four dwords per entry at least -- and handled all the same: the uploads
+    // above read the plan's vectors, so they are waited for before the plan goes.)
+    if (pm::MakeSideLists(in, &plan) != PM_OK) {
+        SetError("per-row item lists beyond 2^32 entries");
+        (void)hipStreamSynchronize(c->stream);
+        plan = pm::BinPlan();
+        return PM_ERR_CAPACITY;
     }
-    PM_TRY(hipMemsetAsync(c->d_sr_slots, 0, desc.size() * sizeof(uint32_t), c->stream));
-    c->frames_on_plan = 0;
-    PM_TRY(hipMemcpyAsync(c->d_sr_desc, desc.data(), desc.size() * sizeof(uint4), hipMemcpyHostToDevice, c->stream));
-    {
-        // Chains of the one-launch grid (four workgroups per CU, all resident): workgroup b bins strip row b; with more strip rows
-        // than workgroups the rows beyond go, heaviest first, to the workgroups whose own row is lightest (by the arena bound,
-        // the only estimate there is) -- a second light row ends before the frame's heaviest row does.
-        std::vector<uint32_t> &nx = c->stage_next_one;
-        const size_t n = desc.size();
-        nx.assign(n, 0u);
-        const size_t resident = static_cast<size_t>(c->n_cus) * c->frame_wg_per_cu;
-        c->one_grid_rows = 0;
-        if (c->one_launch_mode != 0 && resident != 0 && n <= 2 * resident) {  // (only a context that renders one-launch frames pays for their lists)
-            const size_t rows = std::min(n, resident);
-            c->one_grid_rows = static_cast<uint32_t>(rows);
-            if (n > rows) {
-                std::vector<uint32_t> first(rows), extra(n - rows);
-                for (size_t i = 0; i < rows; ++i) first[i] = static_cast<uint32_t>(i);
-                for (size_t i = rows; i < n; ++i) extra[i - rows] = static_cast<uint32_t>(i);
-                auto weight = [&](uint32_t i) { return desc[i].z - desc[i].y; };
-                std::stable_sort(first.begin(), first.end(), [&](uint32_t a, uint32_t b) { return weight(a) < weight(b); });
-                std::stable_sort(extra.begin(), extra.end(), [&](uint32_t a, uint32_t b) { return weight(a) > weight(b); });
-                for (size_t k = 0; k < extra.size(); ++k) nx[first[k]] = extra[k];
-            }
-        }
-        if (c->one_launch_mode != 0 && (n > c->sr_next_one_cap || !c->d_sr_next_one)) {  // (only a context that renders one-launch frames pays for the table)
-            if (c->d_sr_next_one) (void)hipFree(c->d_sr_next_one);
-            c->d_sr_next_one = nullptr;
-            c->sr_next_one_cap = 0;
-            const size_t want = n + n / 4 + 16;
-            PM_TRY(hipMalloc(&c->d_sr_next_one, want * sizeof(uint32_t)));
-            c->sr_next_one_cap = want;
-        }
-        if (c->one_launch_mode != 0) PM_TRY(hipMemcpyAsync(c->d_sr_next_one, nx.data(), n * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    {
-        // the strip rows without a workgroup: the binning launch (clear_in_bin) or a one-launch frame writes their (background) pixels from this list
-        std::vector<uint32_t> &idle = c->stage_idle;
-        idle.clear();
-        std::vector<uint8_t> listed(need.size(), 0);  // (the empty list's one workgroup "has" strip row 0; a strip row cut in two is listed twice)
-        for (const uint4 &d : desc) {
-            const size_t i = static_cast<size_t>(d.x >> 16) * c->strips_x + (d.x & 0xffu);
-            if (i < listed.size()) listed[i] = 1;
-        }
-        for (size_t i = 0; i < need.size() && (c->one_grid_rows != 0 || c->fold_clear_mode >= 3); ++i)
-            if (!listed[i]) idle.push_back(static_cast<uint32_t>(i));
-        c->n_idle_sr = static_cast<uint32_t>(idle.size());
-        if (idle.size() > c->idle_sr_cap || !c->d_idle_sr) {
-            if (c->d_idle_sr) (void)hipFree(c->d_idle_sr);
-            c->d_idle_sr = nullptr;
-            c->idle_sr_cap = 0;
-            const size_t want = idle.size() + idle.size() / 4 + 16;
-            PM_TRY(hipMalloc(&c->d_idle_sr, want * sizeof(uint32_t)));
-            c->idle_sr_cap = want;
-        }
-        if (!idle.empty()) PM_TRY(hipMemcpyAsync(c->d_idle_sr, idle.data(), idle.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-    }
-    c->arena_epoch += 1;  // (a slot's tile_state is reset to "background" on the frame's own stream when the slot is next used)
-    {
-        if (ids.size() > c->band_cap || !c->d_band_bbox) {
-            if (c->d_band_bbox) (void)hipFree(c->d_band_bbox);
-            if (c->d_band_item) (void)hipFree(c->d_band_item);
-            c->d_band_bbox = nullptr;
-            c->d_band_item = nullptr;
-            c->band_cap = 0;
-            const size_t want = ids.size() + ids.size() / 4 + 16;
-            PM_TRY(hipMalloc(&c->d_band_bbox, want * sizeof(uint2)));
-            PM_TRY(hipMalloc(&c->d_band_item, want * sizeof(uint32_t)));
-            c->band_cap = want;
-        }
-        if (!ids.empty() && !c->band_identity) {
-            PM_TRY(hipMemcpyAsync(c->d_band_bbox, bbs.data(), ids.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
-            PM_TRY(hipMemcpyAsync(c->d_band_item, ids.data(), ids.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-        }
-        // Large scenes: every tile row gets its own item list each frame (pm_rowcull_kernel); the
-        // host only sizes the lists, with the kernel's predicate.
-        if (c->use_row_lists) {
-            const uint32_t rows = BandRows(c);
-            // A tile row's scan is cut into parts (workgroups of pm_rowcull_kernel), about four workgroups per CU in all, a part no
-            // shorter than one step of the kernel: rb[r * parts + p] = where part p of row r writes.
-            const uint32_t n_it = static_cast<uint32_t>(bbs.size());
-            const uint32_t parts_wanted = std::max<uint32_t>(1u, (4u * static_cast<uint32_t>(c->n_cus)) / std::max<uint32_t>(rows, 1u));
-            const uint64_t per_part = static_cast<uint64_t>(pm::kRowCullStep) * parts_wanted;
-            // (PM_ROW_LIST_PART_ITEMS: the tests cut small scenes into many parts)
-            const uint32_t part_items = static_cast<uint32_t>(EnvInt("PM_ROW_LIST_PART_ITEMS", static_cast<int>(pm::kRowCullStep * static_cast<uint32_t>(std::max<uint64_t>(1u, (n_it + per_part - 1u) / per_part))), 1, 1 << 30));
-            const uint32_t parts = std::max<uint32_t>(1u, (n_it + part_items - 1u) / part_items);
-            c->row_parts = parts;
-            c->row_part_items = part_items;
-            std::vector<uint32_t> &rb = c->stage_rb;
-            rb.assign(static_cast<size_t>(rows) * parts + 1, 0u);
-            for (uint32_t k = 0; k < n_it; ++k) {
-                const uint2 &b = bbs[k];
-                const uint32_t by = b.x >> 16, bw = b.y >> 16;
-                const uint32_t r_lo = std::max(by / pm::kTileH, c->row0), r_hi = std::min(bw / pm::kTileH, c->row1 - 1);
-                const uint32_t pk = k / part_items;
-                for (uint32_t r = r_lo; r <= r_hi && r_hi >= r_lo; ++r) rb[static_cast<size_t>(r - c->row0) * parts + pk + 1] += 1;
-            }
-            uint64_t run = 0;
-            for (size_t i = 0; i < static_cast<size_t>(rows) * parts; ++i) {
-                const uint32_t n_i = rb[i + 1];
-                rb[i] = static_cast<uint32_t>(run);
-                run += n_i;
-            }
-            if (run > 0xfffffff0ull) {
-                SetError("per-row item lists beyond 2^32 entries");
-                return PM_ERR_CAPACITY;
-            }
-            rb[static_cast<size_t>(rows) * parts] = static_cast<uint32_t>(run);
-            c->row_total = static_cast<uint32_t>(run);
-            if (rb.size() > c->row_base_cap || !c->d_row_base) {  // (grow only)
-                if (c->d_row_base) (void)hipFree(c->d_row_base);
-                c->d_row_base = nullptr;
-                c->row_base_cap = 0;
-                PM_TRY(hipMalloc(&c->d_row_base, (rb.size() + 64) * sizeof(uint32_t)));
-                c->row_base_cap = rb.size() + 64;
-            }
-            PM_TRY(hipMemcpyAsync(c->d_row_base, rb.data(), rb.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-            // every strip row's descriptor gets its tile row's {first entry, entries} next to it
-            std::vector<uint2> &sl = c->stage_list;
-            sl.resize(c->stage_desc.size());
-            for (size_t i = 0; i < sl.size(); ++i) {
-                const uint32_t r = c->stage_desc[i].x >> 16;
-                sl[i] = r < rows ? make_uint2(rb[static_cast<size_t>(r) * parts], rb[static_cast<size_t>(r + 1) * parts] - rb[static_cast<size_t>(r) * parts]) : make_uint2(0u, 0u);
-            }
-            PM_TRY(hipMemcpyAsync(c->d_sr_list, sl.data(), sl.size() * sizeof(uint2), hipMemcpyHostToDevice, c->stream));
-            // (the slots' own list buffers come into being when a slot is next used, EnsureSlotBuffers: the first frame of a
-            //  scene pays for one slot's, not for four -- eight allocations, 0.4 ms of config 5's first frame)
-            c->row_want = std::max<uint64_t>(run, 1);
-        }
+    PM_TRY(UploadList(c, c->sr_desc_whole.p, plan.desc_whole));
+    if (c->one_launch_mode != 0) PM_TRY(UploadList(c, c->sr_next_one.p, plan.next_one));
+    PM_TRY(c->idle_sr.Reserve(plan.idle.size()));
+    PM_TRY(UploadList(c, c->idle_sr.p, plan.idle));
+    if (plan.use_row_lists) {
+        PM_TRY(c->row_base.Reserve(plan.row_base.size(), plan.row_base.size() + 64));
+        PM_TRY(UploadList(c, c->row_base.p, plan.row_base));
+        PM_TRY(UploadList(c, c->sr_list.p, plan.sr_list));
     }
     PM_TRY(hipStreamSynchronize(c->stream));  // ONE wait: the lists are in place before a frame on any stream reads them
-    c->plan_reusable = margin > 0 && c->band_identity;
+    c->frames_on_plan = 0;
+    c->arena_epoch += 1;  // (a slot's tile_state is reset to "background" on the frame's own stream when the slot is next used)
     c->plans_made += 1;
     c->arena_dirty = false;
     c->t_arena_ms = timer.ms();
@@ -1058,23 +662,23 @@ int BuildParams(pm_ctx *c, FrameSlot *s, uint8_t *fb, size_t stride, pm::FramePa
     p->fb_bgra = c->target_fmt == PM_FMT_BGRA8 ? 1u : 0u;
     p->arena = s->d_arena;
     p->arena_cap = s->arena_cap;
-    p->sr_desc = c->d_sr_desc;
-    p->sr_list = c->d_sr_list;
-    p->n_sr_active = c->n_sr_active;
-    p->sr_slots = c->d_sr_slots;
+    p->sr_desc = c->sr_desc.p;
+    p->sr_list = c->sr_list.p;
+    p->n_sr_active = c->plan.n_sr_active();
+    p->sr_slots = c->sr_slots.p;
     p->bin_prio_slots = c->bin_prio_slots;
-    p->bin_grid = c->bin_grid;
-    p->sr_empty_dwords = c->sr_empty_dwords;
+    p->bin_grid = c->plan.bin_grid;
+    p->sr_empty_dwords = c->plan.sr_empty_dwords;
     p->queue = s->d_queue;
     // (the plan's longer work list: the one with the cuts -- the list without them, which frames behind running frames bin from, has fewer entries)
-    p->queue_sub_cap = static_cast<uint32_t>(QueueSubCap(BandTiles(c), std::max(c->n_sr_active, c->n_sr_whole)));
+    p->queue_sub_cap = static_cast<uint32_t>(QueueSubCap(BandTiles(c), std::max(c->plan.n_sr_active(), c->plan.n_sr_whole())));
     if (static_cast<size_t>(pm::kClassCursors) * p->queue_sub_cap > s->queue_cap) {  // (cannot happen: a work list has two entries per strip row at most)
         SetError("the work list is longer than the slot's tile queues were sized for");
         return PM_ERR_CAPACITY;
     }
     p->tile_state = s->d_tile_state;
-    p->tarena = s->d_ptcl;
-    p->tarena_cap = s->ptcl_cap;
+    p->tarena = s->ptcl.p;
+    p->tarena_cap = static_cast<uint32_t>(s->ptcl.cap);
     p->tile_ptcl = s->d_tile_ptcl;
     p->tile_ncmd = s->d_tile_ncmd;
     p->ctr_cur = s->d_ctr + s->parity;
@@ -1086,21 +690,21 @@ int BuildParams(pm_ctx *c, FrameSlot *s, uint8_t *fb, size_t stride, pm::FramePa
     p->fifo = s->d_fifo;
     p->fifo_cap = s->fifo_cap;
     p->one_launch = 0;
-    p->sr_next_one = c->d_sr_next_one;
-    p->one_grid_rows = c->one_grid_rows;
-    p->idle_sr = c->d_idle_sr;
-    p->n_idle_sr = c->n_idle_sr;
+    p->sr_next_one = c->sr_next_one.p;
+    p->one_grid_rows = c->plan.one_grid_rows;
+    p->idle_sr = c->idle_sr.p;
+    p->n_idle_sr = static_cast<uint32_t>(c->plan.idle.size());
     p->spin_ticks = c->frame_spin_ticks;
     // (the whole item list in scene order: the scene's own boxes, no list of indices)
-    p->band_bbox = c->band_identity ? reinterpret_cast<const uint2 *>(c->d_scene + c->dev_bbox_ix) : c->d_band_bbox;
-    p->band_item = c->band_identity ? nullptr : c->d_band_item;
-    p->n_band_items = c->n_band_items;
-    p->bin_waves = c->bin_waves;
+    p->band_bbox = c->plan.band_identity ? reinterpret_cast<const uint2 *>(c->d_scene + c->dev_bbox_ix) : c->band_bbox.p;
+    p->band_item = c->plan.band_identity ? nullptr : c->band_item.p;
+    p->n_band_items = static_cast<uint32_t>(c->plan.band_item.size());
+    p->bin_waves = c->plan.bin_waves;
     // (PM_FOLD_CLEAR=3: a frame whose strip rows are chained -- config 5: lone frame 0.482 -> 0.456 ms -- and, Enqueue, any frame behind
     //  running frames: 4K Tiger sustained +1.5 %.  A small frame alone keeps the fold into the tile kernel's launch: with the
     //  clearing its binning kernel ends a microsecond later, and that is on the frame's critical path.  PM_FOLD_CLEAR=4: always.)
-    p->clear_in_bin = c->fold_clear_mode == 4 || (c->fold_clear_mode == 3 && c->n_sr_active > c->bin_grid) ? 1u : 0u;
-    p->bin_wt = c->bin_wt_mode == 1 || (c->bin_wt_mode == 2 && c->n_sr_active <= c->bin_grid) ? 1u : 0u;
+    p->clear_in_bin = c->fold_clear_mode == 4 || (c->fold_clear_mode == 3 && c->plan.n_sr_active() > c->plan.bin_grid) ? 1u : 0u;
+    p->bin_wt = c->bin_wt_mode == 1 || (c->bin_wt_mode == 2 && c->plan.n_sr_active() <= c->plan.bin_grid) ? 1u : 0u;
     p->split_mode = c->split_mode;
     p->dense_factor = c->dense_factor;
     p->verdict_waves = static_cast<uint32_t>(c->n_cus) * c->fine_wg_per_cu * 4u;
@@ -1110,10 +714,10 @@ int BuildParams(pm_ctx *c, FrameSlot *s, uint8_t *fb, size_t stride, pm::FramePa
         p->handout_static = c->handout == 1 ? 1u : 0u;  // (Enqueue decides per frame when PM_HANDOUT is 0)
     }
     p->fine_grid = FineGrid(c);
-    p->use_row_lists = c->use_row_lists ? 1u : 0u;
-    p->row_base = c->d_row_base;
-    p->row_parts = c->row_parts;
-    p->row_part_items = c->row_part_items;
+    p->use_row_lists = c->plan.use_row_lists ? 1u : 0u;
+    p->row_base = c->row_base.p;
+    p->row_parts = c->plan.row_parts;
+    p->row_part_items = c->plan.row_part_items;
     p->row_bbox = s->d_row_bbox;
     p->row_item = s->d_row_item;
     p->chunk_base = c->d_chunk_base;
@@ -1179,12 +783,12 @@ void ChooseTileKernel(pm_ctx *c, pm::FrameParams *p) {
 // Workgroups of a one-launch frame (0: this frame takes two launches).  Every strip row some item reaches needs its own
 // workgroup, all resident at once; beyond those, as many as there could be tiles to take from the FIFOs.
 uint32_t OneLaunchGrid(const pm_ctx *c) {
-    if (c->one_launch_mode == 0 || c->frame_wg_per_cu == 0 || !c->fused || c->use_row_lists || c->bin_waves != 4) return 0u;
+    if (c->one_launch_mode == 0 || c->frame_wg_per_cu == 0 || !c->fused || c->plan.use_row_lists || c->plan.bin_waves != 4) return 0u;
     const uint32_t resident = static_cast<uint32_t>(c->n_cus) * c->frame_wg_per_cu;
-    if (c->one_grid_rows == 0u) return 0u;  // (more than two strip rows per resident workgroup: EnsureArena)
+    if (c->plan.one_grid_rows == 0u) return 0u;  // (more than two strip rows per resident workgroup: EnsureArena)
     const uint64_t tiles = BandTiles(c);
     if (tiles > 0xffffffu) return 0u;
-    return std::max(c->one_grid_rows, std::min(resident, static_cast<uint32_t>((tiles + 3u) / 4u)));
+    return std::max(c->plan.one_grid_rows, std::min(resident, static_cast<uint32_t>((tiles + 3u) / 4u)));
 }
 
 // The slot's FIFO entries (zeroed once: whoever takes an entry leaves a zero behind).
@@ -1209,31 +813,31 @@ int FeedBackStripRows(pm_ctx *c) {
     if (c->arena_dirty || c->arena_cap == 0) return PM_OK;  // (a new plan is about to be made anyway)
     if (c->frames_on_plan == 0xffffffffu) return PM_OK;
     c->frames_on_plan += 1;
-    if (c->frames_on_plan != 3u || c->bin_split_mode != 1 || c->one_launch_mode != 0 || c->fb_applied || !c->d_sr_slots) return PM_OK;
+    if (c->frames_on_plan != 3u || c->bin_split_mode != 1 || c->one_launch_mode != 0 || c->plan.fb_applied || !c->sr_slots.p) return PM_OK;
     // (only where cutting can happen at all: the plan's rows leave workgroups of the resident grid free, and the band bins from the
     //  one work list -- per-tile-row item lists are addressed by its entries, EnsureArena cuts nothing)
-    if (c->use_row_lists) return PM_OK;
-    if (c->n_sr_active >= static_cast<uint32_t>(c->n_cus) * (c->bin_wg_per_cu == 0xffu ? 5u : std::max(1u, c->bin_wg_per_cu))) return PM_OK;
+    if (c->plan.use_row_lists) return PM_OK;
+    if (c->plan.n_sr_active() >= pm::ResidentBinWorkgroups(c->n_cus, c->bin_wg_per_cu, 1u)) return PM_OK;
     int r = SyncAll(c);
     if (r != PM_OK) return r;
     std::vector<uint32_t> &sl = c->stage_slots;
-    sl.resize(c->n_sr_active);
-    PM_TRY(hipMemcpy(sl.data(), c->d_sr_slots, sl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    sl.resize(c->plan.n_sr_active());
+    PM_TRY(hipMemcpy(sl.data(), c->sr_slots.p, sl.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     const size_t n_rows = static_cast<size_t>(BandRows(c)) * c->strips_x;
     c->fb_slots.assign(n_rows, 0u);
     uint32_t heaviest = 0;
-    for (size_t k = 0; k < sl.size() && k < c->stage_desc.size(); ++k) {
-        const uint32_t x = c->stage_desc[k].x;
+    for (size_t k = 0; k < sl.size() && k < c->plan.desc.size(); ++k) {
+        const uint32_t x = c->plan.desc[k].x;
         const size_t i = static_cast<size_t>(x >> 16) * c->strips_x + (x & 0xffu);
         if (i < n_rows) c->fb_slots[i] += sl[k];  // (a row already cut: its halves' slots)
         if (i < n_rows) heaviest = std::max(heaviest, c->fb_slots[i]);
     }
-    if (heaviest < c->bin_split_slots && c->n_sr_split == 0) {  // nothing to cut, nothing cut: the plan stands
-        c->fb_applied = true;
+    if (heaviest < c->bin_split_slots && c->plan.n_sr_split == 0) {  // nothing to cut, nothing cut: the plan stands
+        c->plan.fb_applied = true;
         return PM_OK;
     }
     c->arena_dirty = true;
-    c->plan_reusable = false;
+    c->plan.reusable = false;
     c->plans_fed_back += 1;
     return PM_OK;
 }
@@ -1346,16 +950,16 @@ int Enqueue(pm_ctx *c, uint8_t *fb, size_t stride, hipStream_t user_stream, hipE
     //  once: such a frame gets a wave for EVERY row and does not walk the chains.)
     // ... from the work list WITHOUT the cuts (a cut strip row is two rows' worth of fixed work: worth it on a lone frame's critical
     // path, a loss where frames overlap): the same arena regions, every cut row whole again
-    uint32_t n_rows_frame = c->n_sr_active;
-    if (p.handout_static && c->n_sr_split != 0 && c->n_sr_whole != 0) {
-        p.sr_desc = c->d_sr_desc_whole;
-        p.n_sr_active = c->n_sr_whole;
-        p.bin_grid = std::min(p.bin_grid, c->n_sr_whole);
+    uint32_t n_rows_frame = c->plan.n_sr_active();
+    if (p.handout_static && c->plan.n_sr_split != 0 && c->plan.n_sr_whole() != 0) {
+        p.sr_desc = c->sr_desc_whole.p;
+        p.n_sr_active = c->plan.n_sr_whole();
+        p.bin_grid = std::min(p.bin_grid, c->plan.n_sr_whole());
         p.sr_slots = nullptr;  // (the report is by entry of the list with the cuts)
-        n_rows_frame = c->n_sr_whole;
+        n_rows_frame = c->plan.n_sr_whole();
     }
-    if (p.handout_static && c->bin_waves_inflight == 1 && c->bin_waves == 4 && n_rows_frame >= 4u * static_cast<uint32_t>(c->n_cus) &&
-        c->plan_cands <= 32ull * n_rows_frame) {
+    if (p.handout_static && c->bin_waves_inflight == 1 && c->plan.bin_waves == 4 && n_rows_frame >= 4u * static_cast<uint32_t>(c->n_cus) &&
+        c->plan.cands <= 32ull * n_rows_frame) {
         if (n_rows_frame <= p.bin_grid) {
             p.bin_waves = 1;
             c->frames_bin_wave_inflight += 1;
@@ -1852,14 +1456,12 @@ pm_ctx *pm_create(int device, int *err) {
         if (e == hipSuccess) c->chunk_bbox_cap = 1u << 19;
         if (e == hipSuccess) e = hipMalloc(&c->d_sup_bbox, (1u << 16) * sizeof(float4));
         if (e == hipSuccess) c->sup_bbox_cap = 1u << 16;
-        if (e == hipSuccess) e = hipMalloc(&c->d_sr_desc, 65536 * sizeof(uint4));
-        if (e == hipSuccess) e = hipMalloc(&c->d_sr_list, 65536 * sizeof(uint2));
-        if (e == hipSuccess) e = hipMalloc(&c->d_sr_slots, 65536 * sizeof(uint32_t));
-        if (e == hipSuccess) e = hipMalloc(&c->d_sr_desc_whole, 65536 * sizeof(uint4));
-        if (e == hipSuccess) c->sr_desc_cap = 65536;
-        if (e == hipSuccess) e = hipMalloc(&c->d_band_bbox, 65536 * sizeof(uint2));
-        if (e == hipSuccess) e = hipMalloc(&c->d_band_item, 65536 * sizeof(uint32_t));
-        if (e == hipSuccess) c->band_cap = 65536;
+        if (e == hipSuccess) e = c->sr_desc.Reserve(65536, 65536);
+        if (e == hipSuccess) e = c->sr_list.Reserve(65536, 65536);
+        if (e == hipSuccess) e = c->sr_slots.Reserve(65536, 65536);
+        if (e == hipSuccess) e = c->sr_desc_whole.Reserve(65536, 65536);
+        if (e == hipSuccess) e = c->band_bbox.Reserve(65536, 65536);
+        if (e == hipSuccess) e = c->band_item.Reserve(65536, 65536);
         // ... and every frame slot's viewport buffers for anything up to 8192 x 8192 (BASELINE config 5: 256 MB of pixels, 70 MB of queues
         // and per-tile tables) and its arenas, sized for config 5 (2.2 GB of worst-case binning regions, 1.7 GB of tile arena): four slots are
         // 16 GB, 6 % of the HBM, and ~0.4 s of pm_create.  A resize within that allocates nothing, whichever slot the next frame lands on
@@ -1891,8 +1493,7 @@ pm_ctx *pm_create(int device, int *err) {
             if (e == hipSuccess) e = hipMalloc(&fs.d_arena, static_cast<size_t>(arena0) * sizeof(uint32_t));
             if (e == hipSuccess) fs.arena_cap = arena0;
             if (e == hipSuccess && !std::getenv("PM_PTCL_INITIAL_CMDS")) {
-                e = hipMalloc(&fs.d_ptcl, static_cast<size_t>(tile0) * sizeof(uint4));
-                if (e == hipSuccess) fs.ptcl_cap = tile0;
+                e = fs.ptcl.Reserve(tile0, tile0);
             }
         }
         if (e != hipSuccess) return fail(e, "working-set reservation");
@@ -1940,11 +1541,7 @@ pm_ctx *pm_create(int device, int *err) {
         c->ptcl_want = 0;
         c->arena_cap = 0;
         if (std::getenv("PM_PTCL_INITIAL_CMDS"))  // tests of the overflow path: what pm_sync grew during the warm-up goes too
-            for (auto &s : c->slot) {
-                if (s.d_ptcl) (void)hipFree(s.d_ptcl);
-                s.d_ptcl = nullptr;
-                s.ptcl_cap = 0;
-            }
+            for (auto &s : c->slot) s.ptcl.Free();
     }
     *err = PM_OK;
     return c;
@@ -1957,21 +1554,21 @@ void pm_destroy(pm_ctx *c) {
     FreeViewport(c);
     for (auto &s : c->slot) {
         if (s.d_arena) (void)hipFree(s.d_arena);
-        if (s.d_ptcl) (void)hipFree(s.d_ptcl);
+        s.ptcl.Free();
         if (s.d_row_bbox) (void)hipFree(s.d_row_bbox);  // (the indices live behind the boxes)
         if (s.d_ctr) (void)hipFree(s.d_ctr);
         if (s.h_overflow) (void)hipHostFree(s.h_overflow);
         if (s.ev_done) (void)hipEventDestroy(s.ev_done);
     }
-    if (c->d_sr_desc) (void)hipFree(c->d_sr_desc);
-    if (c->d_sr_list) (void)hipFree(c->d_sr_list);
-    if (c->d_sr_slots) (void)hipFree(c->d_sr_slots);
-    if (c->d_sr_desc_whole) (void)hipFree(c->d_sr_desc_whole);
-    if (c->d_band_bbox) (void)hipFree(c->d_band_bbox);
-    if (c->d_band_item) (void)hipFree(c->d_band_item);
-    if (c->d_row_base) (void)hipFree(c->d_row_base);
-    if (c->d_idle_sr) (void)hipFree(c->d_idle_sr);
-    if (c->d_sr_next_one) (void)hipFree(c->d_sr_next_one);
+    c->sr_desc.Free();
+    c->sr_list.Free();
+    c->sr_slots.Free();
+    c->sr_desc_whole.Free();
+    c->band_bbox.Free();
+    c->band_item.Free();
+    c->row_base.Free();
+    c->idle_sr.Free();
+    c->sr_next_one.Free();
     c->flatten_cache.Free();
     if (c->d_scene) (void)hipFree(c->d_scene);
     if (c->d_scene_alt) (void)hipFree(c->d_scene_alt);
@@ -2048,9 +1645,9 @@ int pm_upload_scene(pm_ctx *c, size_t bytes) {
     if (r != PM_OK) return r;
     InvalidateScene(c);
     c->fb_slots.clear();  // (another scene: its own frames will say which strip rows are heavy -- a view change, pm_reflatten, keeps the report)
-    c->fb_applied = false;
+    c->plan.fb_applied = false;
     c->replan_wide = false;
-    c->plan_reusable = false;
+    c->plan.reusable = false;
     c->t_flatten_ms = 0;
     // (a context that goes back to host-encoded scenes gives the device flatten's second scene buffer back: round-4 advisor finding)
     if (c->d_scene_alt) {
@@ -2071,9 +1668,9 @@ int pm_flatten_and_encode(pm_ctx *c, const pm_path *paths, size_t n_paths, const
                           const double affine[6], float width_scale, size_t *scene_bytes, uint32_t *n_items) {
     if (!c || !affine || (n_paths && !paths) || (n_els && !els)) return PM_ERR_INVALID;
     c->fb_slots.clear();  // (new paths: their own frames will say which strip rows are heavy)
-    c->fb_applied = false;
+    c->plan.fb_applied = false;
     c->replan_wide = false;
-    c->plan_reusable = false;  // (new paths: planned afresh, for their own boxes)
+    c->plan.reusable = false;  // (new paths: planned afresh, for their own boxes)
     return FlattenAndEncode(c, false, paths, n_paths, els, n_els, nullptr, affine, width_scale, scene_bytes, n_items);
 }
 
@@ -2083,9 +1680,9 @@ int pm_flatten_and_encode_dashed(pm_ctx *c, const pm_path *paths, size_t n_paths
     if (n_dashes == 0) return pm_flatten_and_encode(c, paths, n_paths, els, n_els, affine, width_scale, scene_bytes, n_items);
     if (!c || !affine || (n_paths && !paths) || (n_els && !els) || !dashes || (n_dash_values && !dash_values)) return PM_ERR_INVALID;
     c->fb_slots.clear();
-    c->fb_applied = false;
+    c->plan.fb_applied = false;
     c->replan_wide = false;
-    c->plan_reusable = false;
+    c->plan.reusable = false;
     const pm::DashTable table{dashes, n_dashes, dash_values, n_dash_values};
     return FlattenAndEncode(c, false, paths, n_paths, els, n_els, &table, affine, width_scale, scene_bytes, n_items);
 }
@@ -2383,7 +1980,7 @@ int pm_sync(pm_ctx *c) {
             uint64_t top = 0;
             for (uint32_t i = 0; i < pm::kArenaShards; ++i) top = std::max<uint64_t>(top, k.ptcl[i].top);
             top = (top + 2) * pm::kArenaShards;
-            want = std::max<uint64_t>(want, std::max<uint64_t>(4ull * s.ptcl_cap, 2ull * top));
+            want = std::max<uint64_t>(want, std::max<uint64_t>(4ull * s.ptcl.cap, 2ull * top));
             redo.push_back(s.params);
         }
         for (auto &t : c->slot) t.h_overflow[0] = t.h_overflow[1] = 0;  // (nothing is in flight: every frame that raised one has been looked at or superseded)
@@ -2578,10 +2175,10 @@ int pm_binning_info(pm_ctx *c, uint32_t out[3]) {
 
 int pm_binning_plan_info(pm_ctx *c, uint32_t out[4]) {
     if (!c || !out) return PM_ERR_INVALID;
-    out[0] = c->n_sr_active;
-    out[1] = c->n_sr_split;
+    out[0] = c->plan.n_sr_active();
+    out[1] = c->plan.n_sr_split;
     out[2] = c->plans_fed_back;
-    out[3] = c->fb_applied ? 1u : 0u;
+    out[3] = c->plan.fb_applied ? 1u : 0u;
     return PM_OK;
 }
 
@@ -3830,7 +3427,7 @@ int pm_debug_time_bins(pm_ctx *c, uint64_t *out, size_t max_rows, size_t *n_rows
     if (r != PM_OK) return r;
     r = EnsureArena(c);  // (the work list: one row of the timeline per entry, in the list's order)
     if (r != PM_OK) return r;
-    const size_t rows = std::max<size_t>(static_cast<size_t>(BandRows(c)) * c->strips_x, c->n_sr_active);
+    const size_t rows = std::max<size_t>(static_cast<size_t>(BandRows(c)) * c->strips_x, c->plan.n_sr_active());
     if (n_rows) *n_rows = rows;
     if (rows > max_rows) return PM_ERR_CAPACITY;
     unsigned long long *d = nullptr;

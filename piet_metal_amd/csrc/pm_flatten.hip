@@ -31,6 +31,7 @@
 #include <cstring>
 
 #include "../../include/piet_metal_amd.h"
+#include "pm_dev_array.h"
 #include "pm_flatten.h"
 #include "pm_layout.h"
 
@@ -691,20 +692,6 @@ void FlattenCache::Free() {
     if (h_meta) (void)hipHostFree(h_meta);
     *this = FlattenCache();
 }
-
-namespace {
-template <typename T>
-hipError_t Grow(T **p, size_t *cap, size_t need) {
-    if (need <= *cap && *p) return hipSuccess;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const size_t want = need + (need >> 2) + 16;
-    const hipError_t e = hipMalloc(p, want * sizeof(T));
-    if (e == hipSuccess) *cap = want;
-    return e;
-}
-}  // namespace
 
 // d_u32: el_npts, el_move, el_ptoff(+1), el_mvoff(+1), path_item_base, path_pt_base, sub_first, totals / error / 64-bit point sum (16),
 // the parallel scan's block totals (two words per block of 1 024 elements / paths); then, for the outline stage, {total, plain point
