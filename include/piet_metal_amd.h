@@ -736,6 +736,43 @@ int pm_item_lengths_device(pm_ctx *c, uint32_t flags, void *dev_out, size_t cap,
 int pm_points_at_length_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream);
 int pm_positions_on_edges_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, void *hip_stream);
 
+/* ==== resampling: evenly spaced points along items in one call (decision D26) ====
+ * A request names `count` positions s_0 .. s_{count-1} along `item`, u64 in the unit of path measurement, 2^-16 px, and the record
+ * out[first + j], j < count, is byte for byte what pm_points_at_length answers for {item, 0, s_j} under the same flags: clamped,
+ * degenerate and "none" answers and the unspecified five floats on a segment with a non-finite end included.  Nothing new is said
+ * about what a point is; what is new is that the device makes the positions and walks the item once for all of them.
+ *
+ *   PM_RESAMPLE_STEP  s_j = start + j * step, saturating at 2^64 - 1.  step == 0 is allowed: all positions coincide.
+ *   PM_RESAMPLE_EVEN  start and step must be 0.  T is the item's length (pm_item_lengths); m = count - 1 if the item's kind is
+ *                     PM_MEASURE_OPEN (the last sample is the end), m = count if it is PM_MEASURE_CLOSED (sample `count` would be
+ *                     the start again), and s_j = j * (T div m) + min(j, T mod m) in u64 -- every s_j = 0 where m == 0 and for an
+ *                     item without a walk.  Neighbouring gaps differ by at most one unit, and s_m = T exactly.
+ *
+ * count <= PM_RESAMPLE_MAX_COUNT.  Every request gets a pm_resample_info {length = T, n_unclamped, kind}: kind the item's
+ * PM_MEASURE_* kind, n_unclamped how many of the request's `count` positions have an answer that is not "none" and lacks
+ * PM_MEASURE_CLAMPED -- in step mode how many markers fit.  It counts positions, whether or not out_cap let their records be written.
+ * A request the device cannot answer -- mode > 1, count > PM_RESAMPLE_MAX_COUNT, PM_RESAMPLE_EVEN with a non-zero start or step --
+ * writes no point record at all and has the info {0, 0, PM_RESAMPLE_INVALID}.
+ *
+ * pm_resample_items: the records are packed: q[k].first must be the sum of the counts before it, the total at most out_cap.
+ * flags: PM_HIT_SKIP_TRANSPARENT or 0.  PM_ERR_INVALID, before anything is enqueued: any other flag bit, no resident scene, a NULL q,
+ * out or info with n != 0, a request the device would call invalid, a wrong `first`.  PM_ERR_CAPACITY, with nothing written: the
+ * total exceeds out_cap or 2^20 records (what pm_points_at_length stages at a time).  n == 0 is PM_OK and writes nothing.
+ * Independent of the viewport; frames in flight are not disturbed.  Synchronises. */
+#define PM_RESAMPLE_STEP 0u            /* pm_resample_query.mode */
+#define PM_RESAMPLE_EVEN 1u
+#define PM_RESAMPLE_MAX_COUNT 1048576u /* 2^20 */
+#define PM_RESAMPLE_INVALID 0xffffffffu /* pm_resample_info.kind of a request that cannot be answered */
+typedef struct { uint32_t item, mode, count, first; uint64_t start, step; } pm_resample_query;             /* 32 bytes */
+typedef struct { uint64_t length; uint32_t n_unclamped, kind; } pm_resample_info;                          /* 16 bytes */
+
+int pm_resample_items(pm_ctx *c, const pm_resample_query *q, size_t n, uint32_t flags, pm_length_point *out, size_t out_cap, pm_resample_info *info);
+/* Same on device memory (every pointer 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is.  `first` is the caller's: requests may be laid out freely, in any order, with gaps.  No record with
+ * first + j >= out_cap is ever written, so a bad `first` cannot reach outside the buffer; ranges that overlap are the caller's
+ * business.  The device cannot refuse a request: an invalid one answers as said above. */
+int pm_resample_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

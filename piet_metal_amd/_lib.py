@@ -55,6 +55,9 @@ PM_SNAP_KIND_INTERSECTION, PM_SNAP_KIND_TOO_MANY = 3, 4
 PM_SNAP_MAX_NEAR_EDGES = 512
 PM_MEASURE_NONE, PM_MEASURE_OPEN, PM_MEASURE_CLOSED = 0, 1, 2  # pm_item_length.kind
 PM_MEASURE_FOUND, PM_MEASURE_CLAMPED, PM_MEASURE_DEGENERATE = 1, 2, 4  # status bits of the measure records
+PM_RESAMPLE_STEP, PM_RESAMPLE_EVEN = 0, 1  # pm_resample_query.mode
+PM_RESAMPLE_MAX_COUNT = 1 << 20
+PM_RESAMPLE_INVALID = 0xFFFFFFFF  # pm_resample_info.kind of a request that cannot be answered
 
 
 class PathEl(C.Structure):
@@ -211,6 +214,8 @@ SIGNATURES = {
     "pm_points_at_length_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_positions_on_edges": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p]),
     "pm_positions_on_edges_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pm_resample_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_resample_items_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

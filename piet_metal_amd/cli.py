@@ -14,6 +14,7 @@
     python -m piet_metal_amd.cli tiger out.png --snap 800,800 --snap-radius 12 --snap-to intersections   (the nearest point where two edges cross)
     python -m piet_metal_amd.cli tiger out.png --bounds --select 700,700,900,900   (where is the picture, where the selection, and how many items)
     python -m piet_metal_amd.cli tiger out.png --lengths --point-at 40,37.5        (how long every path is; the point and the tangent 37.5 px along item 40)
+    python -m piet_metal_amd.cli tiger out.png --resample 40,12 --resample-step 40,12.5   (twelve even points along item 40; a point every 12.5 px of it)
     python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -113,17 +114,44 @@ def print_snaps(r, points, radius, to) -> None:
         print(head + f"item {int(s['item'])} path {int(of_item[s['item']])} {what} at {float(s['x']):.9g},{float(s['y']):.9g} d2 {float(s['d2']):.17g}")
 
 
+def point_line(i, d, p, of_item) -> str:
+    """One point record of item i at distance d (pixels) as --point-at prints it."""
+    head = f"item {i} at {d:g}: "
+    if p["item"] == 0xFFFFFFFF:
+        return head + "none"
+    return (head + f"point {float(p['x']):g},{float(p['y']):g} tangent {float(p['tx']):g},{float(p['ty']):g} segment {int(p['index'])} "
+            f"t {float(p['t']):g} path {int(of_item[i])}" + (" (clamped)" if p["status"] & 2 else ""))
+
+
 def print_points_at(r, asks) -> None:
     """--point-at: one line per (item, distance in pixels)."""
     rec = r.points_at_length([a[0] for a in asks], [a[1] for a in asks])
     of_item = r.item_paths()
     for (i, d), p in zip(asks, rec):
-        head = f"item {i} at {d:g}: "
-        if p["item"] == 0xFFFFFFFF:
-            print(head + "none")
+        print(point_line(i, d, p, of_item))
+
+
+def print_resampled(r, even, stepped) -> None:
+    """--resample ITEM,N and --resample-step ITEM,STEP[,START]: per request a line with the item's length in pixels and how many of
+    its points are not clamped, then one line per point as --point-at prints it, at the position the device gave the point."""
+    from .renderer import LENGTH_UNIT, length_units, resample_positions
+
+    of_item = r.item_paths()
+    for asks, mode in ((even, 1), (stepped, 0)):
+        if not asks:
             continue
-        print(head + f"point {float(p['x']):g},{float(p['y']):g} tangent {float(p['tx']):g},{float(p['ty']):g} segment {int(p['index'])} "
-              f"t {float(p['t']):g} path {int(of_item[i])}" + (" (clamped)" if p["status"] & 2 else ""))
+        items = [a[0] for a in asks]
+        if mode == 1:
+            pts, offsets, infos = r.resample(items, [a[1] for a in asks])
+        else:
+            pts, offsets, infos = r.resample_step(items, [a[1] for a in asks], [a[2] for a in asks])
+        for k, (a, info) in enumerate(zip(asks, infos)):
+            n = int(offsets[k + 1] - offsets[k])
+            what = f"{n} even" if mode == 1 else f"every {a[1]:g} from {a[2]:g}"
+            print(f"resample item {a[0]} {what}: length {int(info['length']) / LENGTH_UNIT:g} points {n} unclamped {int(info['n_unclamped'])}")
+            ss = resample_positions(mode, n, int(info["length"]), int(info["kind"]), 0 if mode == 1 else length_units(a[2]), 0 if mode == 1 else length_units(a[1]))
+            for s, p in zip(ss, pts[offsets[k]:offsets[k + 1]]):
+                print(point_line(a[0], s / LENGTH_UNIT, p, of_item))
 
 
 def bounds_record(r, words=None) -> dict:
@@ -176,7 +204,21 @@ def main(argv=None) -> int:
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
     ap.add_argument("--lengths", action="store_true", help="path measurement: print one JSON line {\"paths\": [{\"length\", \"n_items\"}, ...]} -- per path the length in pixels of the geometry it draws (flattened curves, the outlines of styled and dashed strokes, closing segments included) and how many items that is")
     ap.add_argument("--point-at", action="append", default=[], metavar="ITEM,DIST", help="path measurement: print the point DIST pixels along item ITEM, the unit tangent there, the segment it lies on with the parameter along it, and the path the item came from; beyond the item's end: its end, marked (clamped); may be repeated")
+    ap.add_argument("--resample", action="append", default=[], metavar="ITEM,N", help="resampling: print N evenly spaced points along item ITEM -- an open item from its start to its end, a closed one from its start without repeating it -- after a line with the item's length in pixels and how many of the points are not clamped; one line per point as --point-at prints it; may be repeated")
+    ap.add_argument("--resample-step", action="append", default=[], metavar="ITEM,STEP[,START]", help="resampling: the same for a point every STEP pixels along item ITEM from START pixels on (default 0), as many as fit; may be repeated")
     args = ap.parse_args(argv)
+    try:
+        resample_even = [(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.resample]
+        if any(len(p.split(",")) != 2 for p in args.resample) or any(i < 0 or i > 0xFFFFFFFF or not 0 <= n <= 1 << 20 for i, n in resample_even):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--resample takes ITEM,N with 0 <= N <= 1048576")
+    try:
+        resample_step = [(int(p.split(",")[0]), float(p.split(",")[1]), float(p.split(",")[2]) if p.count(",") == 2 else 0.0) for p in args.resample_step]
+        if any(p.count(",") not in (1, 2) for p in args.resample_step) or any(i < 0 or i > 0xFFFFFFFF or not step * 65536 >= 0.5 or not start >= 0 for i, step, start in resample_step):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--resample-step takes ITEM,STEP[,START] with STEP > 0 and START >= 0, in pixels")
     try:
         points_at = [(int(p.split(",")[0]), float(p.split(",")[1])) for p in args.point_at]
         if any(len(p.split(",")) != 2 for p in args.point_at) or any(i < 0 or i > 0xFFFFFFFF for i, _ in points_at):
@@ -281,6 +323,8 @@ def main(argv=None) -> int:
             print(json.dumps({"paths": [{"length": v / 65536, "n_items": c} for v, c in zip(lengths, counts)]}))
         if points_at:  # one line per query: the record, and the <path> the item came from
             print_points_at(r, points_at)
+        if resample_even or resample_step:  # per request a summary line, then one line per point
+            print_resampled(r, resample_even, resample_step)
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

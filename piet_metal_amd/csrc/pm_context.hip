@@ -46,6 +46,7 @@
 #include "pm_snap_cross.h" // pm_cross_kernel: snapping to intersections (the nearest crossing of two edges)
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
 #include "pm_measure.h"    // pm_item_lengths_kernel, pm_points_at_length_kernel, pm_positions_on_edges_kernel: path measurement
+#include "pm_resample.h"   // pm_resample_kernel: many points along an item in one walk
 #include "pm_layout.h"
 
 namespace {
@@ -3314,6 +3315,92 @@ int pm_positions_on_edges(pm_ctx *c, const pm_edge_query *q, size_t n, uint32_t 
         }
     }
     return MeasureToHost(c, pm::LaunchPositionsOnEdges, sizeof(*out), q, n, flags, out);
+}
+
+// ---- resampling (pm_resample.h; decision D26) -------------------------------------------------------------------------------------------
+namespace {
+static_assert(PM_RESAMPLE_STEP == pm::kResampleStep && PM_RESAMPLE_EVEN == pm::kResampleEven && PM_RESAMPLE_MAX_COUNT == pm::kResampleMaxCount &&
+                  PM_RESAMPLE_INVALID == pm::kResampleInvalid,
+              "pm_resample.h's constants are the header's");
+static_assert(sizeof(pm_resample_query) == 32 && offsetof(pm_resample_query, item) == 0 && offsetof(pm_resample_query, mode) == 4 &&
+                  offsetof(pm_resample_query, count) == 8 && offsetof(pm_resample_query, first) == 12 && offsetof(pm_resample_query, start) == 16 &&
+                  offsetof(pm_resample_query, step) == 24,
+              "the request pm_resample_kernel reads");
+static_assert(sizeof(pm_resample_info) == 16 && offsetof(pm_resample_info, length) == 0 && offsetof(pm_resample_info, n_unclamped) == 8 &&
+                  offsetof(pm_resample_info, kind) == 12,
+              "the info pm_resample_kernel writes");
+static_assert(PM_RESAMPLE_MAX_COUNT == kMeasureBatch, "a request fits the staging of pm_points_at_length");
+
+// The launches for n requests in device memory, on q
+int ResampleEnqueue(pm_ctx *c, const uint8_t *d_q, size_t n, uint32_t flags, uint8_t *d_out, size_t out_cap, uint8_t *d_info, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::ResampleParams p{};
+    p.V = QueryView(c, flags);
+    p.out = d_out;
+    p.out_cap = out_cap;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.q = d_q + sizeof(pm_resample_query) * at;
+        p.info = d_info + sizeof(pm_resample_info) * at;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchResample(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_resample_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!dev_q || !dev_info || (!dev_out && out_cap != 0)) {
+        SetError("pm_resample_items_device: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    if (((reinterpret_cast<uintptr_t>(dev_q) | reinterpret_cast<uintptr_t>(dev_out) | reinterpret_cast<uintptr_t>(dev_info)) & 7u) != 0) {
+        SetError("pm_resample_items_device: a device pointer is not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return ResampleEnqueue(c, static_cast<const uint8_t *>(dev_q), n, flags, static_cast<uint8_t *>(dev_out), out_cap, static_cast<uint8_t *>(dev_info),
+                           QueryStream(c, hip_stream));
+}
+
+int pm_resample_items(pm_ctx *c, const pm_resample_query *q, size_t n, uint32_t flags, pm_length_point *out, size_t out_cap, pm_resample_info *info) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!q || !out || !info) {
+        SetError("pm_resample_items: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (q[k].mode > PM_RESAMPLE_EVEN || q[k].count > PM_RESAMPLE_MAX_COUNT || (q[k].mode == PM_RESAMPLE_EVEN && (q[k].start | q[k].step) != 0)) {
+            SetError("pm_resample_items: a request's mode, count, or the start or step of an even request");
+            return PM_ERR_INVALID;
+        }
+        if (q[k].first != total) {   // (a total beyond 2^32 cannot be named by a `first`: refused here)
+            SetError("pm_resample_items: a request's first is not the sum of the counts before it");
+            return PM_ERR_INVALID;
+        }
+        total += q[k].count;
+    }
+    if (total > out_cap || total > kMeasureBatch) return PM_ERR_CAPACITY;
+    // the staging buffer: {records, then per batch of requests: infos, requests}
+    const size_t batch = std::min(n, kMeasureBatch), at_info = total * sizeof(*out), at_q = at_info + batch * sizeof(*info);
+    PM_TRY(QueryStaging(c, at_q + batch * sizeof(*q)));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(c->d_stage + at_q, q + at, m * sizeof(*q), hipMemcpyHostToDevice, c->stream));
+        r = ResampleEnqueue(c, c->d_stage + at_q, m, flags, c->d_stage, total, c->d_stage + at_info, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(info + at, c->d_stage + at_info, m * sizeof(*info), hipMemcpyDeviceToHost, c->stream));
+        if (at + m == n && total != 0) PM_TRY(hipMemcpyAsync(out, c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
 }
 
 int pm_item_paths(pm_ctx *c, uint32_t *path_of_item, size_t cap, uint32_t *n_items) {

@@ -42,6 +42,10 @@ EDGE_QUERY_DTYPE = np.dtype([("item", "<u4"), ("index", "<u4"), ("t", "<f4"), ("
 LENGTH_AT_DTYPE = np.dtype([("s", "<u8"), ("item", "<u4"), ("status", "<u4")])
 assert (ITEM_LENGTH_DTYPE.itemsize, LENGTH_QUERY_DTYPE.itemsize, LENGTH_POINT_DTYPE.itemsize, EDGE_QUERY_DTYPE.itemsize, LENGTH_AT_DTYPE.itemsize) == (16, 16, 32, 16, 16)
 LENGTH_UNIT = 65536  # units of a length per pixel
+# the requests and infos of resampling (decision D26); its records are LENGTH_POINT_DTYPE
+RESAMPLE_QUERY_DTYPE = np.dtype([("item", "<u4"), ("mode", "<u4"), ("count", "<u4"), ("first", "<u4"), ("start", "<u8"), ("step", "<u8")])
+RESAMPLE_INFO_DTYPE = np.dtype([("length", "<u8"), ("n_unclamped", "<u4"), ("kind", "<u4")])
+assert (RESAMPLE_QUERY_DTYPE.itemsize, RESAMPLE_INFO_DTYPE.itemsize) == (32, 16)
 
 
 def length_units(px) -> int:
@@ -52,6 +56,18 @@ def length_units(px) -> int:
         return 0
     f = np.floor(v * np.float64(LENGTH_UNIT) + 0.5)
     return (1 << 64) - 1 if f >= 2.0 ** 64 else int(f)
+
+
+def resample_positions(mode: int, count: int, length: int, kind: int, start: int = 0, step: int = 0) -> list:
+    """D26's positions s_0 .. s_{count-1} of a request, in units of 2^-16 px as Python integers: where the device put the points it
+    answered with.  `length` and `kind` are the request's info record's."""
+    if mode == _lib.PM_RESAMPLE_STEP:
+        return [min(start + j * step, (1 << 64) - 1) for j in range(count)]
+    m = count - 1 if kind == _lib.PM_MEASURE_OPEN else (count if kind == _lib.PM_MEASURE_CLOSED else 0)
+    if m <= 0:
+        return [0] * count
+    d, r = divmod(length, m)
+    return [j * d + min(j, r) for j in range(count)]
 
 
 def _warn_default_stream() -> None:
@@ -867,6 +883,95 @@ class Renderer:
         flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
         s = stream.cuda_stream if stream is not None else None
         _lib.check(self._lib.pm_positions_on_edges_device(self._h, queries.data_ptr(), n, flags, out.data_ptr(), s), "pm_positions_on_edges_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    # ---- resampling (decision D26) -----------------------------------------------------------
+    def _resample(self, q: np.ndarray, skip_transparent: bool):
+        """Packed requests through pm_resample_items: (records LENGTH_POINT_DTYPE [total], offsets int64 [n + 1], infos RESAMPLE_INFO_DTYPE [n])."""
+        offsets = np.zeros(len(q) + 1, np.int64)
+        np.cumsum(q["count"], out=offsets[1:])
+        if offsets[-1] > _lib.PM_RESAMPLE_MAX_COUNT:
+            raise ValueError(f"a resampling call answers at most {_lib.PM_RESAMPLE_MAX_COUNT} samples")
+        q["first"] = offsets[:-1]
+        out = np.zeros(int(offsets[-1]), LENGTH_POINT_DTYPE)
+        info = np.zeros(len(q), RESAMPLE_INFO_DTYPE)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        # (an empty numpy array still has an address: out is never NULL)
+        _lib.check(self._lib.pm_resample_items(self._h, q.ctypes.data, len(q), flags, out.ctypes.data, len(out), info.ctypes.data), "pm_resample_items")
+        return out, offsets, info
+
+    @staticmethod
+    def _resample_requests(items, counts, mode) -> np.ndarray:
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        cn = np.asarray(counts, dtype=np.int64)
+        if cn.ndim not in (0, 1) or (cn.ndim == 1 and len(cn) != len(it)):
+            raise ValueError("one count, or one per item")
+        cn = np.broadcast_to(cn, (len(it),))
+        if len(cn) and (cn.min() < 0 or cn.max() > _lib.PM_RESAMPLE_MAX_COUNT):
+            raise ValueError(f"0 <= count <= {_lib.PM_RESAMPLE_MAX_COUNT}")
+        q = np.zeros(len(it), RESAMPLE_QUERY_DTYPE)
+        q["item"] = it
+        q["mode"] = mode
+        q["count"] = cn
+        return q
+
+    def resample(self, items, counts, skip_transparent: bool = False):
+        """counts[k] evenly spaced points along items[k], in one call and one walk of each item: an open item (Line, Polyline) from its
+        start to its end, both included; a closed one (Fill) from its start, the start not repeated.  Returns (points, offsets,
+        infos): the packed LENGTH_POINT_DTYPE records -- request k's are points[offsets[k]:offsets[k + 1]], each what
+        points_at_units answers at its position --, and per request a RESAMPLE_INFO_DTYPE record {length, n_unclamped, kind}.  The
+        positions are made on the device from the item's own length: s_j = j (T div m) + min(j, T mod m), gaps within one unit of
+        2^-16 px of each other."""
+        return self._resample(self._resample_requests(items, counts, _lib.PM_RESAMPLE_EVEN), skip_transparent)
+
+    def resample_step(self, items, step_px, start_px=0.0, counts=None, skip_transparent: bool = False):
+        """A point every step_px along items[k], the first at start_px (one value each, or one per item; rounded to units of 2^-16 px
+        as points_at_length does).  counts=None: as many as fit -- item_lengths() is called once and item k gets
+        floor((T - start) / step) + 1 samples, 0 where start > T, PM_RESAMPLE_MAX_COUNT at the most (a step that rounds to 0 is
+        refused).  With counts given nothing is read back first: positions beyond the end answer with the end and the
+        clamped bit, and infos["n_unclamped"] says how many fitted.  Returns what resample returns."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        n = len(it) if it.ndim == 1 else 0
+        sp, st = np.asarray(step_px, dtype=np.float64), np.asarray(start_px, dtype=np.float64)
+        for v in (sp, st):
+            if v.ndim not in (0, 1) or (v.ndim == 1 and len(v) != n):
+                raise ValueError("one step and one start, or one per item")
+        steps = [length_units(v) for v in np.broadcast_to(sp, (n,))]
+        starts = [length_units(v) for v in np.broadcast_to(st, (n,))]
+        if counts is None:
+            total = self.item_lengths(skip_transparent)["length"]
+            counts = []
+            for i, step, start in zip(it.tolist(), steps, starts):
+                T = int(total[i]) if i < len(total) else 0
+                if step == 0:
+                    raise ValueError("a step that rounds to 0 fits any number of samples: give counts")
+                counts.append(0 if start > T else min((T - start) // step + 1, _lib.PM_RESAMPLE_MAX_COUNT))
+        q = self._resample_requests(it, counts, _lib.PM_RESAMPLE_STEP)
+        q["start"] = np.array(starts, dtype=np.uint64)
+        q["step"] = np.array(steps, dtype=np.uint64)
+        return self._resample(q, skip_transparent)
+
+    def resample_tensor(self, requests, out, info, stream=None, skip_transparent: bool = False) -> None:
+        """Resampling on torch CUDA tensors, asynchronous: requests int32 [n, 8] (the 32-byte RESAMPLE_QUERY_DTYPE records), out int32
+        [cap, 8] (LENGTH_POINT_DTYPE records), info int32 [n, 4] (RESAMPLE_INFO_DTYPE), all contiguous.  A request's `first` is the
+        caller's: sample j goes to out[first + j], and no row at or beyond cap is written.  An invalid request writes no point and
+        gets the info kind PM_RESAMPLE_INVALID.  `stream` as in hit_test_tensor."""
+        if not (requests.is_cuda and out.is_cuda and info.is_cuda) or str(requests.dtype) != "torch.int32" or requests.dim() != 2 or requests.shape[1] != 8 or \
+                not requests.is_contiguous():
+            raise TypeError("resample_tensor needs a contiguous CUDA int32 tensor [n, 8]")
+        n = requests.shape[0]
+        if str(out.dtype) != "torch.int32" or out.dim() != 2 or out.shape[1] != 8 or not out.is_contiguous():
+            raise TypeError("resample_tensor writes a contiguous CUDA int32 tensor [cap, 8]")
+        if str(info.dtype) != "torch.int32" or tuple(info.shape) != (n, 4) or not info.is_contiguous():
+            raise TypeError("resample_tensor writes a contiguous CUDA int32 tensor [n, 4] of infos")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_resample_items_device(self._h, requests.data_ptr(), n, flags, out.data_ptr(), out.shape[0], info.data_ptr(), s),
+                   "pm_resample_items_device")
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
