@@ -105,3 +105,15 @@ def test_edge_scenes_under_emulation(built):
     assert " passed" in out and "failed" not in out
     out = _run("edge_scenes", {"PM_EMU_CUS": "2"}, workers="8", test_file="test_edge_scenes.py")
     assert " passed" in out and "failed" not in out
+
+
+def test_frame_structure_under_emulation(built):
+    """tests/test_frame_structure.py: every scene of part A at the list, candidate and fragment edges of the frame kernels (ladders
+    thinned, every edge kept) through the single-wave path, a workgroup, the dense kernel, unfused and as one launch; the turns
+    ladder at 1 024 and 2 047 turns, one staircase, 65 536 segments of one item in one tile, one turn beyond the limit -- and the
+    one-launch scenes again on two CUs.  It judges the kernels' logic at those edges; LDS atomics on the packed word, cross-lane
+    hand-overs and the four waves' exchange are the -m gpu run's."""
+    out = _run("frame_structure", workers="8", test_file="test_frame_structure.py")
+    assert " passed" in out and "failed" not in out
+    out = _run("frame_structure and one_launch", {"PM_EMU_CUS": "2"}, workers="8", test_file="test_frame_structure.py")
+    assert " passed" in out and "failed" not in out
