@@ -773,6 +773,54 @@ int pm_resample_items(pm_ctx *c, const pm_resample_query *q, size_t n, uint32_t 
  * business.  The device cannot refuse a request: an invalid one answers as said above. */
 int pm_resample_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream);
 
+/* ==== trimming: the piece of an item between two lengths (decision D27) ====
+ * A request names a piece [lo, hi] of `item` in the unit of path measurement, 2^-16 px, and gets the geometry between the two
+ * positions: the vertices of the walk's segments that overlap the piece, in the order of the walk, as poly-line runs.  Lengths,
+ * segments k, their ends a and b, q_k, Q_k, T and the kind are path measurement's (D25) as they are.
+ *
+ *   PM_TRIM_RANGE  lo = min(s0, T), hi = min(s1, T); s0 > s1 is invalid.  {0, 2^64 - 1} is the whole item.
+ *   PM_TRIM_PART   s0 = j, s1 = m, 1 <= m <= PM_TRIM_MAX_PARTS, j < m: piece j of m even ones, [b_j, b_j+1] with
+ *                  b_i = i * (T div m) + min(i, T mod m) -- pm_resample_items' even positions.  The m pieces tile [0, T] exactly.
+ *
+ * Segment k is covered iff Q_k < hi and Q_k + q_k > lo: an overlap of positive length, or, for q_k == 0, lo < Q_k < hi.  lo >= hi
+ * covers nothing (the empty piece).  A covered k has A_k -- a's stored pair if lo <= Q_k, else pm_points_at_length's point at lo --
+ * and B_k -- b's stored pair if hi >= Q_k + q_k, else the point at hi.  For every covered k in increasing order A_k is emitted, with
+ * PM_TRIM_MOVE, iff k is the first covered segment or A_k differs from the B of the covered segment before (compared as f32 values:
+ * -0 equals 0, a NaN nothing); then B_k is emitted.  So a piece is a list of runs without doubled joints, and a run breaks where the
+ * walk jumps: between the sub-paths of a compound Fill.  Wrap-around on a closed item is two requests.
+ *
+ * A vertex is a pm_trim_vertex {x, y, index = k, flags}: PM_TRIM_MOVE starts a run, PM_TRIM_CUT says the vertex is interpolated
+ * (on a segment with a non-finite end its x, y are not promised).  Vertex number p of a piece goes to out[first + p] iff p < cap and
+ * first + p < out_cap; nothing else of the buffer is touched.  Every request gets a pm_trim_info {length = T, n_vertices, n_runs,
+ * kind, flags}: the counts are of the whole piece, whatever was written (cap = 0 is the count pass); flags PM_TRIM_TRUNCATED (some
+ * vertex was not written) and PM_TRIM_END_CLAMPED (range mode with s1 > T).  A request the device cannot answer writes no vertex and
+ * has an info of zeros with kind PM_TRIM_INVALID.  The length of a piece re-measured from its vertices is not promised to be hi - lo:
+ * cut ends are rounded to f32.
+ *
+ * pm_trim_items: the vertices are packed: q[k].first must be the sum of the caps before it, the total at most out_cap.  flags:
+ * PM_HIT_SKIP_TRANSPARENT or 0.  PM_ERR_INVALID, before anything is enqueued: any other flag bit, no resident scene, a NULL q or info
+ * with n != 0, a NULL out with a non-zero total, a request the device would call invalid, a wrong `first`.  PM_ERR_CAPACITY, with
+ * nothing written: the total exceeds out_cap or 2^20 records.  n == 0 is PM_OK and writes nothing.  Independent of the viewport;
+ * frames in flight are not disturbed.  Synchronises. */
+#define PM_TRIM_RANGE 0u               /* pm_trim_query.mode */
+#define PM_TRIM_PART 1u
+#define PM_TRIM_MAX_PARTS 1048576u     /* 2^20 */
+#define PM_TRIM_MOVE 1u                /* pm_trim_vertex.flags */
+#define PM_TRIM_CUT 2u
+#define PM_TRIM_TRUNCATED 1u           /* pm_trim_info.flags */
+#define PM_TRIM_END_CLAMPED 2u
+#define PM_TRIM_INVALID 0xffffffffu    /* pm_trim_info.kind of a request that cannot be answered */
+typedef struct { uint32_t item, mode, first, cap; uint64_t s0, s1; } pm_trim_query;                         /* 32 bytes */
+typedef struct { float x, y; uint32_t index, flags; } pm_trim_vertex;                                      /* 16 bytes */
+typedef struct { uint64_t length; uint32_t n_vertices, n_runs, kind, flags; } pm_trim_info;                /* 24 bytes */
+
+int pm_trim_items(pm_ctx *c, const pm_trim_query *q, size_t n, uint32_t flags, pm_trim_vertex *out, size_t out_cap, pm_trim_info *info);
+/* Same on device memory (every pointer 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is.  `first` and `cap` are the caller's: pieces may be laid out freely, in any order, with gaps.  No record at
+ * or beyond out_cap is ever written; ranges that overlap are the caller's business.  The device cannot refuse a request: an invalid
+ * one answers as said above. */
+int pm_trim_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

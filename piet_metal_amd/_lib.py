@@ -58,6 +58,11 @@ PM_MEASURE_FOUND, PM_MEASURE_CLAMPED, PM_MEASURE_DEGENERATE = 1, 2, 4  # status 
 PM_RESAMPLE_STEP, PM_RESAMPLE_EVEN = 0, 1  # pm_resample_query.mode
 PM_RESAMPLE_MAX_COUNT = 1 << 20
 PM_RESAMPLE_INVALID = 0xFFFFFFFF  # pm_resample_info.kind of a request that cannot be answered
+PM_TRIM_RANGE, PM_TRIM_PART = 0, 1  # pm_trim_query.mode
+PM_TRIM_MAX_PARTS = 1 << 20
+PM_TRIM_MOVE, PM_TRIM_CUT = 1, 2  # pm_trim_vertex.flags
+PM_TRIM_TRUNCATED, PM_TRIM_END_CLAMPED = 1, 2  # pm_trim_info.flags
+PM_TRIM_INVALID = 0xFFFFFFFF  # pm_trim_info.kind of a request that cannot be answered
 
 
 class PathEl(C.Structure):
@@ -216,6 +221,8 @@ SIGNATURES = {
     "pm_positions_on_edges_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_resample_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_resample_items_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_trim_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_trim_items_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

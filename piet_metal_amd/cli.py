@@ -15,6 +15,7 @@
     python -m piet_metal_amd.cli tiger out.png --bounds --select 700,700,900,900   (where is the picture, where the selection, and how many items)
     python -m piet_metal_amd.cli tiger out.png --lengths --point-at 40,37.5        (how long every path is; the point and the tangent 37.5 px along item 40)
     python -m piet_metal_amd.cli tiger out.png --resample 40,12 --resample-step 40,12.5   (twelve even points along item 40; a point every 12.5 px of it)
+    python -m piet_metal_amd.cli tiger out.png --trim 40,10,25.5 --trim-parts 40,4   (item 40 between 10 and 25.5 px along it; item 40 in four even pieces)
     python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -154,6 +155,35 @@ def print_resampled(r, even, stepped) -> None:
                 print(point_line(a[0], s / LENGTH_UNIT, p, of_item))
 
 
+def vertex_line(v) -> str:
+    """One trimmed vertex as --trim prints it."""
+    return (f"  {'move' if v['flags'] & 1 else 'line'} {float(v['x']):g},{float(v['y']):g} segment {int(v['index'])}" + (" (cut)" if v["flags"] & 2 else ""))
+
+
+def print_trimmed(r, ranges, parts) -> None:
+    """--trim ITEM,START,END and --trim-parts ITEM,M: per piece a header line with its ends and the item's length in pixels and how
+    many vertices and runs it has, then one line per vertex."""
+    from .renderer import LENGTH_UNIT
+
+    if ranges:
+        vs, offsets, infos = r.trim([a[0] for a in ranges], [a[1] for a in ranges], [a[2] for a in ranges])
+        for k, (a, info) in enumerate(zip(ranges, infos)):
+            print(f"trim item {a[0]} [{a[1]:g}, {a[2]:g}]: length {int(info['length']) / LENGTH_UNIT:g} vertices {int(info['n_vertices'])} runs {int(info['n_runs'])}")
+            for v in vs[offsets[k]:offsets[k + 1]]:
+                print(vertex_line(v))
+    k = 0
+    if parts:
+        vs, offsets, infos = r.trim_parts([a[0] for a in parts], [a[1] for a in parts])
+    for i, m in parts:
+        for j in range(m):
+            T = int(infos[k]["length"])
+            a, b = (j * (T // m) + min(j, T % m)) / LENGTH_UNIT, ((j + 1) * (T // m) + min(j + 1, T % m)) / LENGTH_UNIT
+            print(f"trim item {i} [{a:g}, {b:g}]: length {T / LENGTH_UNIT:g} vertices {int(infos[k]['n_vertices'])} runs {int(infos[k]['n_runs'])}")
+            for v in vs[offsets[k]:offsets[k + 1]]:
+                print(vertex_line(v))
+            k += 1
+
+
 def bounds_record(r, words=None) -> dict:
     """--bounds: the box and the counts of the whole scene (words None) or of the items whose word is non-zero."""
     box, n_items, n_boxed = r.selection_bounds(words)
@@ -206,9 +236,23 @@ def main(argv=None) -> int:
     ap.add_argument("--point-at", action="append", default=[], metavar="ITEM,DIST", help="path measurement: print the point DIST pixels along item ITEM, the unit tangent there, the segment it lies on with the parameter along it, and the path the item came from; beyond the item's end: its end, marked (clamped); may be repeated")
     ap.add_argument("--resample", action="append", default=[], metavar="ITEM,N", help="resampling: print N evenly spaced points along item ITEM -- an open item from its start to its end, a closed one from its start without repeating it -- after a line with the item's length in pixels and how many of the points are not clamped; one line per point as --point-at prints it; may be repeated")
     ap.add_argument("--resample-step", action="append", default=[], metavar="ITEM,STEP[,START]", help="resampling: the same for a point every STEP pixels along item ITEM from START pixels on (default 0), as many as fit; may be repeated")
+    ap.add_argument("--trim", action="append", default=[], metavar="ITEM,START,END", help="trimming: print the piece of item ITEM between START and END pixels along it (END may be inf) -- a header line with the item's length in pixels and the piece's numbers of vertices and runs, then one line per vertex: 'move' starts a run, '(cut)' marks an interpolated end; may be repeated")
+    ap.add_argument("--trim-parts", action="append", default=[], metavar="ITEM,M", help="trimming: the same for each of M even pieces of item ITEM, in order; may be repeated")
     args = ap.parse_args(argv)
     try:
-        resample_even = [(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.resample]
+        trim_ranges = [(int(p.split(",")[0]), float(p.split(",")[1]), float(p.split(",")[2])) for p in args.trim]
+        if any(p.count(",") != 2 for p in args.trim) or any(i < 0 or i > 0xFFFFFFFF or not start >= 0 or not end >= start for i, start, end in trim_ranges):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--trim takes ITEM,START,END with 0 <= START <= END, in pixels")
+    try:
+        trim_parts = [(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.trim_parts]
+        if any(p.count(",") != 1 for p in args.trim_parts) or any(i < 0 or i > 0xFFFFFFFF or not 1 <= m <= 1 << 20 for i, m in trim_parts):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--trim-parts takes ITEM,M with 1 <= M <= 1048576")
+    try:
+        resample_even =[(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.resample]
         if any(len(p.split(",")) != 2 for p in args.resample) or any(i < 0 or i > 0xFFFFFFFF or not 0 <= n <= 1 << 20 for i, n in resample_even):
             raise ValueError
     except (ValueError, IndexError):
@@ -325,6 +369,8 @@ def main(argv=None) -> int:
             print_points_at(r, points_at)
         if resample_even or resample_step:  # per request a summary line, then one line per point
             print_resampled(r, resample_even, resample_step)
+        if trim_ranges or trim_parts:  # per piece a header line, then one line per vertex
+            print_trimmed(r, trim_ranges, trim_parts)
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)

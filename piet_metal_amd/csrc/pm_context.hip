@@ -47,6 +47,7 @@
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
 #include "pm_measure.h"    // pm_item_lengths_kernel, pm_points_at_length_kernel, pm_positions_on_edges_kernel: path measurement
 #include "pm_resample.h"   // pm_resample_kernel: many points along an item in one walk
+#include "pm_trim.h"       // pm_trim_kernel: the piece of an item between two lengths
 #include "pm_layout.h"
 
 namespace {
@@ -3399,6 +3400,119 @@ int pm_resample_items(pm_ctx *c, const pm_resample_query *q, size_t n, uint32_t 
         PM_TRY(hipMemcpyAsync(info + at, c->d_stage + at_info, m * sizeof(*info), hipMemcpyDeviceToHost, c->stream));
         if (at + m == n && total != 0) PM_TRY(hipMemcpyAsync(out, c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
         PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    return PM_OK;
+}
+
+// ---- trimming (pm_trim.h; decision D27) ---------------------------------------------------------------------------------------------------
+namespace {
+static_assert(PM_TRIM_RANGE == pm::kTrimRange && PM_TRIM_PART == pm::kTrimPart && PM_TRIM_MAX_PARTS == pm::kTrimMaxParts && PM_TRIM_INVALID == pm::kTrimInvalid &&
+                  PM_TRIM_MOVE == pm::kTrimMove && PM_TRIM_CUT == pm::kTrimCut && PM_TRIM_TRUNCATED == pm::kTrimTruncated &&
+                  PM_TRIM_END_CLAMPED == pm::kTrimEndClamped,
+              "pm_trim.h's constants are the header's");
+static_assert(sizeof(pm_trim_query) == 32 && offsetof(pm_trim_query, item) == 0 && offsetof(pm_trim_query, mode) == 4 && offsetof(pm_trim_query, first) == 8 &&
+                  offsetof(pm_trim_query, cap) == 12 && offsetof(pm_trim_query, s0) == 16 && offsetof(pm_trim_query, s1) == 24,
+              "the request pm_trim_kernel reads");
+static_assert(sizeof(pm_trim_vertex) == 16 && offsetof(pm_trim_vertex, x) == 0 && offsetof(pm_trim_vertex, y) == 4 && offsetof(pm_trim_vertex, index) == 8 &&
+                  offsetof(pm_trim_vertex, flags) == 12,
+              "the vertex pm_trim_kernel writes");
+static_assert(sizeof(pm_trim_info) == 24 && offsetof(pm_trim_info, length) == 0 && offsetof(pm_trim_info, n_vertices) == 8 && offsetof(pm_trim_info, n_runs) == 12 &&
+                  offsetof(pm_trim_info, kind) == 16 && offsetof(pm_trim_info, flags) == 20,
+              "the info pm_trim_kernel writes");
+
+// Would the device call the request invalid
+bool TrimInvalid(const pm_trim_query &r) {
+    if (r.mode == PM_TRIM_RANGE) return r.s0 > r.s1;
+    return r.mode != PM_TRIM_PART || r.s1 == 0 || r.s1 > PM_TRIM_MAX_PARTS || r.s0 >= r.s1;
+}
+
+// The launches for n requests in device memory, on q
+int TrimEnqueue(pm_ctx *c, const uint8_t *d_q, size_t n, uint32_t flags, uint8_t *d_out, size_t out_cap, uint8_t *d_info, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::TrimParams p{};
+    p.V = QueryView(c, flags);
+    p.out = d_out;
+    p.out_cap = out_cap;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.q = d_q + sizeof(pm_trim_query) * at;
+        p.info = d_info + sizeof(pm_trim_info) * at;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchTrim(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_trim_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!dev_q || !dev_info || (!dev_out && out_cap != 0)) {
+        SetError("pm_trim_items_device: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    if (((reinterpret_cast<uintptr_t>(dev_q) | reinterpret_cast<uintptr_t>(dev_out) | reinterpret_cast<uintptr_t>(dev_info)) & 7u) != 0) {
+        SetError("pm_trim_items_device: a device pointer is not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return TrimEnqueue(c, static_cast<const uint8_t *>(dev_q), n, flags, static_cast<uint8_t *>(dev_out), out_cap, static_cast<uint8_t *>(dev_info),
+                       QueryStream(c, hip_stream));
+}
+
+int pm_trim_items(pm_ctx *c, const pm_trim_query *q, size_t n, uint32_t flags, pm_trim_vertex *out, size_t out_cap, pm_trim_info *info) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!q || !info) {
+        SetError("pm_trim_items: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (TrimInvalid(q[k])) {
+            SetError("pm_trim_items: a request's mode, a range with s0 > s1, or a part j of m without 1 <= m <= 2^20 and j < m");
+            return PM_ERR_INVALID;
+        }
+        if (q[k].first != total) {   // (a total beyond 2^32 cannot be named by a `first`: refused here)
+            SetError("pm_trim_items: a request's first is not the sum of the caps before it");
+            return PM_ERR_INVALID;
+        }
+        total += q[k].cap;
+    }
+    if (total != 0 && !out) {
+        SetError("pm_trim_items: out is NULL with vertices to write");
+        return PM_ERR_INVALID;
+    }
+    if (total > out_cap || total > kMeasureBatch) return PM_ERR_CAPACITY;
+    // the staging buffer: {vertices, then per batch of requests: infos, requests}
+    const size_t batch = std::min(n, kMeasureBatch), at_info = total * sizeof(*out), at_q = at_info + batch * sizeof(*info);
+    PM_TRY(QueryStaging(c, at_q + batch * sizeof(*q)));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(c->d_stage + at_q, q + at, m * sizeof(*q), hipMemcpyHostToDevice, c->stream));
+        r = TrimEnqueue(c, c->d_stage + at_q, m, flags, c->d_stage, total, c->d_stage + at_info, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(info + at, c->d_stage + at_info, m * sizeof(*info), hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (total == 0) return PM_OK;
+    // a piece shorter than its cap leaves rows of its range that the device did not write: those stay the caller's
+    bool exact = true;
+    for (size_t k = 0; k < n && exact; ++k) exact = info[k].n_vertices >= q[k].cap;
+    if (exact) {
+        PM_TRY(hipMemcpyAsync(out, c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+        return PM_OK;
+    }
+    std::vector<pm_trim_vertex> got(total);
+    PM_TRY(hipMemcpyAsync(got.data(), c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n; ++k) {
+        const size_t wrote = std::min<size_t>(q[k].cap, info[k].n_vertices);
+        if (wrote != 0) std::memcpy(out + q[k].first, got.data() + q[k].first, wrote * sizeof(*out));
     }
     return PM_OK;
 }

@@ -46,6 +46,11 @@ LENGTH_UNIT = 65536  # units of a length per pixel
 RESAMPLE_QUERY_DTYPE = np.dtype([("item", "<u4"), ("mode", "<u4"), ("count", "<u4"), ("first", "<u4"), ("start", "<u8"), ("step", "<u8")])
 RESAMPLE_INFO_DTYPE = np.dtype([("length", "<u8"), ("n_unclamped", "<u4"), ("kind", "<u4")])
 assert (RESAMPLE_QUERY_DTYPE.itemsize, RESAMPLE_INFO_DTYPE.itemsize) == (32, 16)
+# the requests, vertices and infos of trimming (decision D27)
+TRIM_QUERY_DTYPE = np.dtype([("item", "<u4"), ("mode", "<u4"), ("first", "<u4"), ("cap", "<u4"), ("s0", "<u8"), ("s1", "<u8")])
+TRIM_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("index", "<u4"), ("flags", "<u4")])
+TRIM_INFO_DTYPE = np.dtype([("length", "<u8"), ("n_vertices", "<u4"), ("n_runs", "<u4"), ("kind", "<u4"), ("flags", "<u4")])
+assert (TRIM_QUERY_DTYPE.itemsize, TRIM_VERTEX_DTYPE.itemsize, TRIM_INFO_DTYPE.itemsize) == (32, 16, 24)
 
 
 def length_units(px) -> int:
@@ -68,6 +73,17 @@ def resample_positions(mode: int, count: int, length: int, kind: int, start: int
         return [0] * count
     d, r = divmod(length, m)
     return [j * d + min(j, r) for j in range(count)]
+
+
+def trim_runs(vertices) -> list:
+    """The poly-line runs of trimmed vertices (TRIM_VERTEX_DTYPE, one piece or several in a row): split at every PM_TRIM_MOVE into a
+    list of float32 (n, 2) arrays, each what Encoder.polyline takes."""
+    v = np.asarray(vertices)
+    starts = np.flatnonzero(v["flags"] & _lib.PM_TRIM_MOVE)
+    xy = np.stack([v["x"], v["y"]], axis=1).astype(np.float32, copy=False) if len(v) else np.zeros((0, 2), np.float32)
+    if len(v) and (len(starts) == 0 or starts[0] != 0):
+        raise ValueError("the first vertex of a piece starts a run")
+    return [xy[a:b] for a, b in zip(starts.tolist(), starts.tolist()[1:] + [len(v)])]
 
 
 def _warn_default_stream() -> None:
@@ -972,6 +988,105 @@ class Renderer:
         s = stream.cuda_stream if stream is not None else None
         _lib.check(self._lib.pm_resample_items_device(self._h, requests.data_ptr(), n, flags, out.data_ptr(), out.shape[0], info.data_ptr(), s),
                    "pm_resample_items_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    # ---- trimming (decision D27) -------------------------------------------------------------
+    def _trim(self, q: np.ndarray, skip_transparent: bool):
+        """Requests through pm_trim_items twice: the count pass (cap = 0), then exactly packed.  Returns (vertices TRIM_VERTEX_DTYPE
+        [total], offsets int64 [n + 1], infos TRIM_INFO_DTYPE [n])."""
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        info = np.zeros(len(q), TRIM_INFO_DTYPE)
+        q["first"] = 0
+        q["cap"] = 0
+        _lib.check(self._lib.pm_trim_items(self._h, q.ctypes.data, len(q), flags, None, 0, info.ctypes.data), "pm_trim_items")
+        offsets = np.zeros(len(q) + 1, np.int64)
+        np.cumsum(info["n_vertices"], out=offsets[1:])
+        if offsets[-1] > 1 << 20:
+            raise ValueError(f"a trimming call answers at most {1 << 20} vertices")
+        q["first"] = offsets[:-1]
+        q["cap"] = info["n_vertices"]
+        out = np.zeros(int(offsets[-1]), TRIM_VERTEX_DTYPE)
+        if len(out):
+            _lib.check(self._lib.pm_trim_items(self._h, q.ctypes.data, len(q), flags, out.ctypes.data, len(out), info.ctypes.data), "pm_trim_items")
+        return out, offsets, info
+
+    def trim_units(self, items, s0, s1, skip_transparent: bool = False):
+        """The pieces [min(s0[k], T), min(s1[k], T)] of items[k], positions in units of 2^-16 px as integers (one value each, or one
+        per item; s0 <= s1; 2^64 - 1 is "to the end").  Returns (vertices, offsets, infos): the packed TRIM_VERTEX_DTYPE records --
+        piece k's are vertices[offsets[k]:offsets[k + 1]], poly-line runs that trim_runs splits --, and per piece a TRIM_INFO_DTYPE
+        record {length, n_vertices, n_runs, kind, flags}."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        ends = []
+        for v in (s0, s1):
+            a = np.asarray(v, dtype=object)
+            if a.ndim not in (0, 1) or (a.ndim == 1 and len(a) != len(it)):
+                raise ValueError("one position, or one per item")
+            vals = [int(x) for x in np.broadcast_to(a, (len(it),)).tolist()]
+            if any(not 0 <= x < 1 << 64 for x in vals):
+                raise ValueError("0 <= position < 2^64")
+            ends.append(vals)
+        if any(a > b for a, b in zip(*ends)):
+            raise ValueError("a piece's start is not beyond its end")
+        q = np.zeros(len(it), TRIM_QUERY_DTYPE)
+        q["item"] = it
+        q["mode"] = _lib.PM_TRIM_RANGE
+        q["s0"] = np.array(ends[0], dtype=np.uint64)
+        q["s1"] = np.array(ends[1], dtype=np.uint64)
+        return self._trim(q, skip_transparent)
+
+    def trim(self, items, starts_px, ends_px, skip_transparent: bool = False):
+        """trim_units with the positions in pixels (rounded to units of 2^-16 px as points_at_length does; an end of inf is "to the
+        end"): the geometry of items[k] between the two lengths."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        n = len(it) if it.ndim == 1 else 0
+        units = []
+        for v in (starts_px, ends_px):
+            a = np.asarray(v, dtype=np.float64)
+            if a.ndim not in (0, 1) or (a.ndim == 1 and len(a) != n):
+                raise ValueError("one position, or one per item")
+            units.append([length_units(x) for x in np.broadcast_to(a, (n,))])
+        return self.trim_units(it, units[0], units[1], skip_transparent)
+
+    def trim_parts(self, items, parts, skip_transparent: bool = False):
+        """Every item of `items` cut into parts[k] even pieces (one count, or one per item; 1 <= parts <= PM_TRIM_MAX_PARTS): the
+        pieces of item k in order, then those of item k + 1, in what trim_units returns.  The pieces of an item tile [0, T] exactly,
+        and their ends are resample()'s even positions."""
+        it = np.ascontiguousarray(items, dtype=np.uint32)
+        if it.ndim != 1:
+            raise ValueError("items is a 1-D array of item indices")
+        m = np.asarray(parts, dtype=np.int64)
+        if m.ndim not in (0, 1) or (m.ndim == 1 and len(m) != len(it)):
+            raise ValueError("one number of parts, or one per item")
+        m = np.broadcast_to(m, (len(it),))
+        if len(m) and (m.min() < 1 or m.max() > _lib.PM_TRIM_MAX_PARTS):
+            raise ValueError(f"1 <= parts <= {_lib.PM_TRIM_MAX_PARTS}")
+        q = np.zeros(int(m.sum()), TRIM_QUERY_DTYPE)
+        q["item"] = np.repeat(it, m)
+        q["mode"] = _lib.PM_TRIM_PART
+        q["s0"] = np.concatenate([np.arange(k, dtype=np.uint64) for k in m.tolist()]) if len(q) else 0
+        q["s1"] = np.repeat(m, m).astype(np.uint64)
+        return self._trim(q, skip_transparent)
+
+    def trim_tensor(self, requests, out, info, stream=None, skip_transparent: bool = False) -> None:
+        """Trimming on torch CUDA tensors, asynchronous: requests int32 [n, 8] (the 32-byte TRIM_QUERY_DTYPE records), out int32
+        [cap, 4] (TRIM_VERTEX_DTYPE records), info int32 [n, 6] (TRIM_INFO_DTYPE), all contiguous.  A request's `first` and `cap` are
+        the caller's: vertex p goes to out[first + p] for p < cap, and no row at or beyond the tensor's end is written.  An invalid
+        request writes no vertex and gets the info kind PM_TRIM_INVALID.  `stream` as in hit_test_tensor."""
+        if not (requests.is_cuda and out.is_cuda and info.is_cuda) or str(requests.dtype) != "torch.int32" or requests.dim() != 2 or requests.shape[1] != 8 or \
+                not requests.is_contiguous():
+            raise TypeError("trim_tensor needs a contiguous CUDA int32 tensor [n, 8]")
+        n = requests.shape[0]
+        if str(out.dtype) != "torch.int32" or out.dim() != 2 or out.shape[1] != 4 or not out.is_contiguous():
+            raise TypeError("trim_tensor writes a contiguous CUDA int32 tensor [cap, 4]")
+        if str(info.dtype) != "torch.int32" or tuple(info.shape) != (n, 6) or not info.is_contiguous():
+            raise TypeError("trim_tensor writes a contiguous CUDA int32 tensor [n, 6] of infos")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_trim_items_device(self._h, requests.data_ptr(), n, flags, out.data_ptr(), out.shape[0], info.data_ptr(), s), "pm_trim_items_device")
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
