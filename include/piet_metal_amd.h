@@ -574,6 +574,33 @@ int pm_hit_rects_stack(pm_ctx *c, const float *rects /* n x {x0, y0, x1, y1} */,
 int pm_hit_stack_device(pm_ctx *c, const void *dev_xy, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream);
 int pm_hit_rects_stack_device(pm_ctx *c, const void *dev_rects, size_t n, uint32_t k, uint32_t flags, void *dev_items, void *dev_n_hit, void *hip_stream);
 
+/* ==== coverage counts: covered and visible pixels per item (decision D28) ====
+ * "How much of this item can be seen at all": a layer panel's hidden objects, dropping occluded items before export, pixel areas, a
+ * pixel to scroll to.  For the pixel rectangle (x0, y0, w, h) let H(p) be the items that contain the centre of pixel p as pm_hit_frame
+ * means it (PM_HIT_SKIP_TRANSPARENT included); an item is OPAQUE as pm_hit_stack means it (a Circle or ellipse always, a Line, Fill
+ * or Polyline if the alpha byte of its colour is 255).  One record per item i in flat paint order:
+ *   covered        pixels p with i in H(p);
+ *   visible        pixels with i in H(p) and no opaque j > i in H(p): i is in pm_hit_stack's answer at that centre with
+ *                  PM_HIT_STOP_AT_OPAQUE and unbounded k;
+ *   top            pixels with i = max H(p): the histogram of pm_hit_frame's top_item;
+ *   first_visible  the smallest j * w + i' over the pixels (x0 + i', y0 + j) counted in visible, PM_HIT_NONE if there are none.
+ * top <= visible <= covered; the counts add up over disjoint rectangles.  Integer sums and a minimum: the bytes do not depend on the
+ * launch.  With PM_COVERAGE_VISIBLE_ONLY, a flag of these two calls alone (every other call refuses it as unknown), covered is DEFINED
+ * to equal visible and the walk of a tile may end once all of it lies under opaque items: "which items are hidden", cheaply.
+ * Output discipline is pm_item_bounds': *n_items (may be NULL) is always set; PM_ERR_CAPACITY if cap < n_items, and then nothing is
+ * written; records beyond n_items are not written.  The call initialises the records it writes: it never accumulates.  w == 0 or
+ * h == 0 is PM_OK and writes n_items records {0, 0, 0, PM_HIT_NONE}.  PM_ERR_INVALID, before anything is enqueued: flag bits other
+ * than these two, no resident scene, x0 + w > 65536 or y0 + h > 65536, w * h > 2^32 - 1 (the counts are 32-bit), a NULL out with
+ * n_items > 0.  Independent of the viewport as pm_hit_frame is; frames in flight are not disturbed.  Synchronises. */
+#define PM_COVERAGE_VISIBLE_ONLY 16u
+typedef struct { uint32_t covered, visible, top, first_visible; } pm_coverage;   /* 16 bytes */
+int pm_item_coverage(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, pm_coverage *out, size_t cap,
+                     uint32_t *n_items);
+/* Same into device memory (4-byte aligned, else PM_ERR_INVALID), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_test_device is. */
+int pm_item_coverage_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, void *dev_out, size_t cap,
+                            void *hip_stream);
+
 /* ==== polygon queries: lasso selection, a marquee in a rotated view (decision D20) ====
  * The query polygon K has m vertices xy = m x {x, y} in scene coordinates, 3 <= m <= PM_POLYGON_MAX_VERTICES (else
  * PM_ERR_INVALID), and closes itself.  K TOUCHES an item if the item's outline reaches K's boundary, a point of the item lies in

@@ -45,6 +45,7 @@ PM_HIT_NONE = 0xFFFFFFFF
 PM_HIT_SKIP_TRANSPARENT = 1
 PM_HIT_STOP_AT_OPAQUE = 8  # a flag of the stack calls
 PM_HIT_STACK_MAX = 256
+PM_COVERAGE_VISIBLE_ONLY = 16  # a flag of the coverage calls
 PM_SEL_TOUCHES = 1
 PM_SEL_ENCLOSES = 2
 PM_SEL_EVEN_ODD = 2  # a flag of the polygon calls
@@ -198,6 +199,8 @@ SIGNATURES = {
     "pm_hit_stack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pm_hit_rects_stack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pm_hit_rects_stack_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pm_item_coverage": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
+    "pm_item_coverage_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_select_rect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                  C.POINTER(C.c_uint32)]),
     "pm_select_rect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),

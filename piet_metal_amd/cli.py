@@ -232,6 +232,8 @@ def main(argv=None) -> int:
     ap.add_argument("--bounds", action="store_true", help="bounds: print one JSON line with the box {x0, y0, x1, y1} (pixels) of everything that is drawn and how many items it has -- \"scene\" -- and, with --select / --lasso, the same for the items the query touches -- \"selection\"; with --fit: of the fitted view")
     ap.add_argument("--fit", action="store_true", help="zoom to fit: before rendering, change the view so that the box of everything drawn -- with --select / --lasso: of what the query touches in the view as given -- fills the output, centred; what --select / --lasso print is what they touched in the view as given")
     ap.add_argument("--item-map", default=None, metavar="OUT.npy", help="save the item map of the rendered view -- uint32 [height, width], the topmost item under every pixel's centre, 0xffffffff where there is none (numpy.save) -- and print how many distinct items are visible and how many pixels show none; with --frames: of the last frame")
+    ap.add_argument("--coverage", action="store_true", help="coverage counts: for every item that covers a pixel of the rendered view print its index, the path it came from, how many pixel centres it covers, on how many of them it is under no opaque item (visible), on how many it is the topmost item (top), and the first pixel X,Y that shows it; with --frames: of the first frame")
+    ap.add_argument("--hidden", action="store_true", help="coverage counts: print the indices of the items no pixel of the rendered view shows -- outside it, or wholly under opaque items")
     ap.add_argument("--lengths", action="store_true", help="path measurement: print one JSON line {\"paths\": [{\"length\", \"n_items\"}, ...]} -- per path the length in pixels of the geometry it draws (flattened curves, the outlines of styled and dashed strokes, closing segments included) and how many items that is")
     ap.add_argument("--point-at", action="append", default=[], metavar="ITEM,DIST", help="path measurement: print the point DIST pixels along item ITEM, the unit tangent there, the segment it lies on with the parameter along it, and the path the item came from; beyond the item's end: its end, marked (clamped); may be repeated")
     ap.add_argument("--resample", action="append", default=[], metavar="ITEM,N", help="resampling: print N evenly spaced points along item ITEM -- an open item from its start to its end, a closed one from its start without repeating it -- after a line with the item's length in pixels and how many of the points are not clamped; one line per point as --point-at prints it; may be repeated")
@@ -371,6 +373,10 @@ def main(argv=None) -> int:
             print_resampled(r, resample_even, resample_step)
         if trim_ranges or trim_parts:  # per piece a header line, then one line per vertex
             print_trimmed(r, trim_ranges, trim_parts)
+        if args.coverage:  # one line per item that covers a pixel of the view
+            print_coverage(r, args)
+        if args.hidden:  # one line: the items no pixel of the view shows
+            print("hidden: " + (" ".join(str(int(i)) for i in r.hidden_items(0, 0, args.width, args.height)) or "none"))
         if args.frames <= 1:
             if args.item_map:
                 save_item_map(r, args)
@@ -402,6 +408,19 @@ def main(argv=None) -> int:
             save_item_map(r, args)
         print(f"{stem}-###.png: {args.frames} frames {args.width}x{args.height}, re-encode + render {t_gpu / args.frames * 1e3:.2f} ms per frame", file=sys.stderr)
     return 0
+
+
+def print_coverage(r, args) -> None:
+    """--coverage: per item that covers a pixel of the view its index, the path it came from where there is one, the three counts
+    and the first pixel that shows it."""
+    cov = r.item_coverage(0, 0, args.width, args.height)
+    of_item = r.item_paths()
+    for i in np.flatnonzero(cov["covered"]):
+        rec = cov[i]
+        path = f" path {int(of_item[i])}" if i < len(of_item) and of_item[i] != 0xFFFFFFFF else ""
+        first = int(rec["first_visible"])
+        at = "none" if first == 0xFFFFFFFF else f"{first % args.width},{first // args.width}"
+        print(f"item {int(i)}{path}: covered {int(rec['covered'])} visible {int(rec['visible'])} top {int(rec['top'])} first_visible {at}")
 
 
 def save_item_map(r, args) -> None:

@@ -42,6 +42,7 @@
 #include "pm_hit_rect.h"   // pm_hit_rects_kernel, pm_select_rect_kernel: rectangle queries (pick with a tolerance, marquee selection)
 #include "pm_hit_poly.h"   // pm_select_polygon_kernel: polygon queries (lasso, rotated marquee)
 #include "pm_hit_stack.h"  // pm_hit_stack_kernel, pm_hit_rects_stack_kernel: hit stacks (the k topmost items under a point or rectangle)
+#include "pm_coverage.h"   // pm_item_coverage_kernel: covered, visible and topmost pixels per item, a workgroup per 16 x 16 tile
 #include "pm_snap.h"       // pm_snap_kernel: snapping (the nearest vertex or edge to a cursor)
 #include "pm_snap_cross.h" // pm_cross_kernel: snapping to intersections (the nearest crossing of two edges)
 #include "pm_bounds.h"     // pm_item_bounds_kernel, pm_union_bounds_kernel: item, selection and group boxes
@@ -2467,6 +2468,7 @@ static_assert(PM_HIT_SKIP_TRANSPARENT == pm::kHitSkipTransparent && PM_HIT_NONE 
                   PM_SEL_ENCLOSES == pm::kSelEncloses && PM_POLYGON_MAX_VERTICES == pm::kPolyMaxVertices,
               "pm_query_common.h's and pm_hit_poly.h's constants are the header's");
 static_assert(PM_HIT_STOP_AT_OPAQUE == pm::kHitStopAtOpaque && PM_HIT_STACK_MAX == pm::kHitStackMax, "pm_hit_stack.h's constants are the header's");
+static_assert(PM_COVERAGE_VISIBLE_ONLY == pm::kCoverageVisibleOnly && sizeof(pm_coverage) == 4 * pm::kCoverageWords, "pm_coverage.h's constants are the header's");
 static_assert(PM_SNAP_VERTICES == pm::kSnapVertices && PM_SNAP_EDGES == pm::kSnapEdges && PM_SNAP_KIND_VERTEX == pm::kSnapKindVertex &&
                   PM_SNAP_KIND_EDGE == pm::kSnapKindEdge,
               "pm_snap.h's constants are the header's");
@@ -2760,6 +2762,82 @@ int pm_hit_frame(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, ui
         PM_TRY(hipMemcpy2D(top_item + at * stride, stride * 4, d_top, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
         if (n_hit) PM_TRY(hipMemcpy2D(n_hit + at * stride, stride * 4, d_cnt, static_cast<size_t>(w) * 4, static_cast<size_t>(w) * 4, m, hipMemcpyDeviceToHost));
     }
+    return PM_OK;
+}
+
+// ---- coverage counts (pm_item_coverage_kernel, pm_coverage.h; decision D28) ------------------------------------------------------
+namespace {
+static_assert(sizeof(pm_coverage) == 16 && offsetof(pm_coverage, covered) == 0 && offsetof(pm_coverage, visible) == 4 && offsetof(pm_coverage, top) == 8 &&
+                  offsetof(pm_coverage, first_visible) == 12,
+              "the record pm_item_coverage_kernel writes");
+
+// What both coverage calls refuse about the flags, the scene and the rectangle, before anything is enqueued
+int CoverageCheck(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags) {
+    if (flags & ~static_cast<uint32_t>(PM_HIT_SKIP_TRANSPARENT | PM_COVERAGE_VISIBLE_ONLY)) {
+        SetError("pm_item_coverage: unknown flag bits");
+        return PM_ERR_INVALID;
+    }
+    const int r = SceneResident(c);
+    if (r != PM_OK) return r;
+    if (static_cast<uint64_t>(x0) + w > 65536u || static_cast<uint64_t>(y0) + h > 65536u) {
+        SetError("pm_item_coverage: the rectangle ends beyond pixel 65 535");
+        return PM_ERR_INVALID;
+    }
+    if (static_cast<uint64_t>(w) * h > 0xffffffffull) {
+        SetError("pm_item_coverage: more than 2^32 - 1 pixels (the counts are 32-bit)");
+        return PM_ERR_INVALID;
+    }
+    return PM_OK;
+}
+
+// The launches for a rectangle of pixels, on q: the records' initial value, then the tiles
+int CoverageEnqueue(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, uint32_t *d_out, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::CoverageParams p{};
+    p.V = QueryView(c, flags);
+    p.out = d_out;
+    p.x0 = x0;
+    p.y0 = y0;
+    p.w = w;
+    p.h = h;
+    pm::LaunchItemCoverage(p, static_cast<uint32_t>(c->n_cus), q);
+    return QueryOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_item_coverage_device(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, void *dev_out, size_t cap, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = CoverageCheck(c, x0, y0, w, h, flags);
+    if (r != PM_OK) return r;
+    if (cap < c->n_items) return PM_ERR_CAPACITY;
+    if (c->n_items == 0) return PM_OK;
+    if (!dev_out || (reinterpret_cast<uintptr_t>(dev_out) & 3u) != 0) {
+        SetError("pm_item_coverage_device: dev_out is NULL or not 4-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return CoverageEnqueue(c, x0, y0, w, h, flags, static_cast<uint32_t *>(dev_out), QueryStream(c, hip_stream));
+}
+
+int pm_item_coverage(pm_ctx *c, uint32_t x0, uint32_t y0, uint32_t w, uint32_t h, uint32_t flags, pm_coverage *out, size_t cap, uint32_t *n_items) {
+    if (!c) return PM_ERR_INVALID;
+    if (n_items) *n_items = c->scene_bytes >= 8 ? c->n_items : 0u;
+    PM_TRY(hipSetDevice(c->device));
+    int r = CoverageCheck(c, x0, y0, w, h, flags);
+    if (r != PM_OK) return r;
+    const size_t n = c->n_items;
+    if (cap < n) return PM_ERR_CAPACITY;
+    if (n == 0) return PM_OK;
+    if (!out) {
+        SetError("pm_item_coverage: out is NULL");
+        return PM_ERR_INVALID;
+    }
+    PM_TRY(QueryStaging(c, n * sizeof(pm_coverage)));
+    r = CoverageEnqueue(c, x0, y0, w, h, flags, reinterpret_cast<uint32_t *>(c->d_stage), c->stream);
+    if (r != PM_OK) return r;
+    PM_TRY(hipMemcpyAsync(out, c->d_stage, n * sizeof(pm_coverage), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
     return PM_OK;
 }
 

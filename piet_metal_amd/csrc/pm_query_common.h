@@ -1,4 +1,4 @@
-// What the query kernels share: pm_hit_test.h, pm_hit_frame.h, pm_hit_rect.h, pm_hit_poly.h, pm_hit_stack.h, pm_snap.h, pm_snap_cross.h,
+// What the query kernels share: pm_hit_test.h, pm_hit_frame.h, pm_hit_rect.h, pm_hit_poly.h, pm_hit_stack.h, pm_coverage.h, pm_snap.h, pm_snap_cross.h,
 // pm_bounds.h, pm_measure.h, pm_resample.h and pm_trim.h.  None of them is on the frame path: they read the scene and the scene index (pm_index_kernel), nothing a frame
 // writes.  Included by pm_context.hip through those headers, in whose unit the kernels are compiled.
 //

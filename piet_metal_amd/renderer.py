@@ -34,6 +34,9 @@ assert SNAP_CROSS_DTYPE.itemsize == 48
 # pm_label_bounds (decision D22): what Renderer.union_bounds returns, 40 bytes a record
 LABEL_BOUNDS_DTYPE = np.dtype([("box", "<f8", (4,)), ("n_items", "<u4"), ("n_boxed", "<u4")])
 assert LABEL_BOUNDS_DTYPE.itemsize == 40
+# pm_coverage (decision D28): what Renderer.item_coverage returns, 16 bytes a record
+COVERAGE_DTYPE = np.dtype([("covered", "<u4"), ("visible", "<u4"), ("top", "<u4"), ("first_visible", "<u4")])
+assert COVERAGE_DTYPE.itemsize == 16
 # the records and queries of path measurement (decision D25): lengths and positions are integers in units of 2^-16 px
 ITEM_LENGTH_DTYPE = np.dtype([("length", "<u8"), ("n_segments", "<u4"), ("kind", "<u4")])
 LENGTH_QUERY_DTYPE = np.dtype([("item", "<u4"), ("reserved", "<u4"), ("s", "<u8")])
@@ -532,6 +535,51 @@ class Renderer:
         """hit_stack with a tolerance: the k topmost items that come within the square of half side `tolerance` around each point
         (hit_rects_stack on pick's squares)."""
         return self.hit_rects_stack(self._pick_rects(points, tolerance), k, skip_transparent=skip_transparent, stop_at_opaque=stop_at_opaque, counts=counts)
+
+    # ---- coverage counts (decision D28) ----------------------------------------------------
+    @staticmethod
+    def _coverage_flags(skip_transparent, visible_only) -> int:
+        return (_lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0) | (_lib.PM_COVERAGE_VISIBLE_ONLY if visible_only else 0)
+
+    @staticmethod
+    def _coverage_rect(name, x0, y0, w, h):
+        x0, y0, w, h = (operator.index(v) for v in (x0, y0, w, h))
+        if min(x0, y0, w, h) < 0 or x0 + w > 65536 or y0 + h > 65536 or w * h > 0xFFFFFFFF:
+            raise ValueError(f"{name} needs a rectangle inside [0, 65536) x [0, 65536) of fewer than 2^32 pixels")
+        return x0, y0, w, h
+
+    def item_coverage(self, x0: int, y0: int, w: int, h: int, skip_transparent: bool = False, visible_only: bool = False) -> np.ndarray:
+        """How much of every item can be seen in the pixel rectangle [x0, x0 + w) x [y0, y0 + h): a structured array
+        (COVERAGE_DTYPE), one record per item in flat paint order -- `covered`, the pixels whose centre the item contains (what
+        hit_frame counts); `visible`, those of them under no opaque item above it (a circle, or a colour of alpha 255: hit_stack's
+        stop_at_opaque); `top`, those where it is the topmost item (the histogram of hit_frame's map); `first_visible`, the smallest
+        j * w + i over the visible pixels (x0 + i, y0 + j), PM_HIT_NONE if there are none.  visible_only: `covered` is DEFINED to
+        equal `visible`, and tiles that lie under opaque items are left early -- cheaper on deep scenes.  Needs a scene, no
+        viewport."""
+        x0, y0, w, h = self._coverage_rect("item_coverage", x0, y0, w, h)
+        out = np.empty(self.stats()["n_items"], COVERAGE_DTYPE)
+        _lib.check(self._lib.pm_item_coverage(self._h, x0, y0, w, h, self._coverage_flags(skip_transparent, visible_only), out.ctypes.data, len(out), None),
+                   "pm_item_coverage")
+        return out
+
+    def item_coverage_tensor(self, out, x0: int = 0, y0: int = 0, w: int = 0, h: int = 0, stream=None, skip_transparent: bool = False,
+                             visible_only: bool = False) -> None:
+        """The same into a torch CUDA tensor, asynchronous: out int32 or uint32 [m, 4] with m >= n_items, contiguous, a row
+        {covered, visible, top, first_visible} per item; rows beyond n_items are not written.  `stream` as in hit_test_tensor."""
+        if not (out.is_cuda and out.element_size() == 4 and not out.is_floating_point() and out.dim() == 2 and out.shape[1] == 4 and out.is_contiguous()):
+            raise TypeError("item_coverage_tensor writes a contiguous CUDA tensor [m, 4] of 32-bit integers")
+        x0, y0, w, h = self._coverage_rect("item_coverage_tensor", x0, y0, w, h)
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_item_coverage_device(self._h, x0, y0, w, h, self._coverage_flags(skip_transparent, visible_only), out.data_ptr(), out.shape[0], s),
+                   "pm_item_coverage_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def hidden_items(self, x0: int, y0: int, w: int, h: int, skip_transparent: bool = False) -> np.ndarray:
+        """The indices of the items no pixel of the rectangle shows: outside it, or wholly under opaque items (item_coverage with
+        visible_only, visible == 0)."""
+        return np.flatnonzero(self.item_coverage(x0, y0, w, h, skip_transparent=skip_transparent, visible_only=True)["visible"] == 0)
 
     def select_rect(self, x0, y0, x1, y1, skip_transparent: bool = False):
         """Marquee selection: (touched, enclosed), bool arrays over the items in flat paint order -- every item the closed rectangle
