@@ -848,6 +848,50 @@ int pm_trim_items(pm_ctx *c, const pm_trim_query *q, size_t n, uint32_t flags, p
  * one answers as said above. */
 int pm_trim_items_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream);
 
+/* ==== item crossings: every point where two items' edges cross (decision D29) ====
+ * A request names two items and gets every crossing of an edge of A with an edge of B; item_a == item_b asks for the item's
+ * self-crossings, each pair of edges i < j once.  The edges of an item are the segments of path measurement's walk (D25) under D21's
+ * names (item, k) with both ends finite; K(item), the size of the range k runs over, is 1 for a Line, the number of points less one
+ * for a Polyline, the number of entries (separators included) for a Fill, and 0 for everything without a walk: a Circle or ellipse, a
+ * one-point Polyline, an item the flags skip, an index >= the number of items.  No request is invalid.
+ *
+ * A pair e = (A, i): a -> b, f = (B, j): c -> d is a crossing iff (1) the edges' boxes meet, max(a.x, b.x) >= min(c.x, d.x),
+ * max(c.x, d.x) >= min(a.x, b.x) and the same in y, on the stored f32 values; (2) the edges share no end (an end of e equal to an end
+ * of f in both f32 coordinates); (3) pm_snap_intersections' arithmetic in binary64, one rounding per operation: r = b - a, s = d - c,
+ * den = rx sy - ry sx != 0, w = c - a, t = (wx sy - wy sx) / den, u = (wx ry - wy rx) / den, 0 <= t <= 1 and 0 <= u <= 1.
+ * T-junctions count; parallel, collinear and degenerate edges give none.  The point is X = a + r t.
+ *
+ * The record is a pm_crossing: its first and its second 16 bytes are each a pm_edge_query {item, index, t, 0} that
+ * pm_positions_on_edges takes as it is; then x, y (X rounded to f32), side (PM_CROSSING_SIDE_POS if den > 0, PM_CROSSING_SIDE_NEG if
+ * den < 0: which way B crosses A) and a zero word.  The crossings of a request are numbered p = 0, 1, ... by (i, j) ascending, and
+ * record p goes to out[first + p] iff p < cap and first + p < out_cap; nothing else of the buffer is touched.  Every request gets a
+ * pm_crossings_info {n_crossings, flags, n_a = K(A), n_b = K(B)}: n_crossings counts the whole answer, whatever was written (cap = 0
+ * is the count pass); flags PM_CROSSINGS_TRUNCATED (some record was not written) and PM_CROSSINGS_TOO_MANY: K(A) * K(B) exceeds
+ * PM_CROSSINGS_MAX_PAIRS, no pair was looked at, n_crossings is 0 and nothing is written -- split the item with pm_trim_items.
+ * {B, A} answers what {A, B} does with the roles exchanged: the same pairs, t and u exchanged bit for bit, side 1 <-> 2; x and y are
+ * computed from the other edge and may differ in the last bit.
+ *
+ * pm_item_crossings: the records are packed: q[k].first must be the sum of the caps before it, the total at most out_cap.  flags:
+ * PM_HIT_SKIP_TRANSPARENT or 0.  PM_ERR_INVALID, before anything is enqueued: any other flag bit, no resident scene, a NULL q or info
+ * with n != 0, a NULL out with a non-zero total, a wrong `first`.  PM_ERR_CAPACITY, with nothing written: the total exceeds out_cap or
+ * 2^20 records.  n == 0 is PM_OK and writes nothing.  Independent of the viewport; frames in flight are not disturbed.  Synchronises. */
+#define PM_CROSSINGS_TRUNCATED 1u          /* pm_crossings_info.flags */
+#define PM_CROSSINGS_TOO_MANY 2u
+#define PM_CROSSINGS_MAX_PAIRS 268435456u  /* 2^28 */
+#define PM_CROSSING_SIDE_POS 1u            /* pm_crossing.side */
+#define PM_CROSSING_SIDE_NEG 2u
+typedef struct { uint32_t item_a, item_b, first, cap; } pm_crossings_query;                                  /* 16 bytes */
+typedef struct { uint32_t item_a, index_a; float t; uint32_t reserved_a;
+                 uint32_t item_b, index_b; float u; uint32_t reserved_b;
+                 float x, y; uint32_t side, reserved; } pm_crossing;                                         /* 48 bytes */
+typedef struct { uint32_t n_crossings, flags, n_a, n_b; } pm_crossings_info;                                 /* 16 bytes */
+
+int pm_item_crossings(pm_ctx *c, const pm_crossings_query *q, size_t n, uint32_t flags, pm_crossing *out, size_t out_cap, pm_crossings_info *info);
+/* Same on device memory (every pointer 8-byte aligned), asynchronous on hip_stream (NULL: the context's stream), ordered as
+ * pm_hit_rects_device is.  `first` and `cap` are the caller's: answers may be laid out freely, in any order, with gaps.  No record at
+ * or beyond out_cap is ever written; ranges that overlap are the caller's business.  A request is one wave's work. */
+int pm_item_crossings_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream);
+
 /* For a scene made by pm_flatten_and_encode / pm_reflatten: path_of_item[i] = index into the `paths` array that
  * produced item i.  *n_items is always set; PM_ERR_CAPACITY if cap < n_items; PM_ERR_INVALID for a scene that came
  * from pm_upload_scene (or no scene at all). */

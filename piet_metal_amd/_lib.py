@@ -64,6 +64,9 @@ PM_TRIM_MAX_PARTS = 1 << 20
 PM_TRIM_MOVE, PM_TRIM_CUT = 1, 2  # pm_trim_vertex.flags
 PM_TRIM_TRUNCATED, PM_TRIM_END_CLAMPED = 1, 2  # pm_trim_info.flags
 PM_TRIM_INVALID = 0xFFFFFFFF  # pm_trim_info.kind of a request that cannot be answered
+PM_CROSSINGS_TRUNCATED, PM_CROSSINGS_TOO_MANY = 1, 2  # pm_crossings_info.flags
+PM_CROSSINGS_MAX_PAIRS = 1 << 28
+PM_CROSSING_SIDE_POS, PM_CROSSING_SIDE_NEG = 1, 2  # pm_crossing.side
 
 
 class PathEl(C.Structure):
@@ -226,6 +229,8 @@ SIGNATURES = {
     "pm_resample_items_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_trim_items": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pm_trim_items_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "pm_item_crossings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pm_item_crossings_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "pm_item_paths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]),
     "pm_layout_selfcheck": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]),
     "pm_get_scene_timings": (C.c_int, [C.c_void_p, C.POINTER(SceneTimings)]),

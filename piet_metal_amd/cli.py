@@ -16,6 +16,7 @@
     python -m piet_metal_amd.cli tiger out.png --lengths --point-at 40,37.5        (how long every path is; the point and the tangent 37.5 px along item 40)
     python -m piet_metal_amd.cli tiger out.png --resample 40,12 --resample-step 40,12.5   (twelve even points along item 40; a point every 12.5 px of it)
     python -m piet_metal_amd.cli tiger out.png --trim 40,10,25.5 --trim-parts 40,4   (item 40 between 10 and 25.5 px along it; item 40 in four even pieces)
+    python -m piet_metal_amd.cli tiger out.png --crossings 40,41 --self-crossings 40   (where item 40 crosses item 41, and where it crosses itself)
     python -m piet_metal_amd.cli tiger out.png --fit                               (zoom to fit; with --select / --lasso: zoom to the selection)
 
 Replaces the reference's MTKView shell (TestApp/ViewController.m, PietRenderer.m:90-101) for a
@@ -184,6 +185,27 @@ def print_trimmed(r, ranges, parts) -> None:
             k += 1
 
 
+def crossing_line(c, s_a: int) -> str:
+    """One crossing as --crossings prints it: the point, the edge and the parameter on either item, how far along A it lies in pixels,
+    and which way B crosses A."""
+    from .renderer import LENGTH_UNIT
+
+    return (f"  {float(c['x']):g},{float(c['y']):g} a segment {int(c['index_a'])} t {float(c['t']):g} at {int(s_a) / LENGTH_UNIT:g}"
+            f" b segment {int(c['index_b'])} u {float(c['u']):g} side {'+' if int(c['side']) == 1 else '-'}")
+
+
+def print_crossings(r, pairs) -> None:
+    """--crossings A,B and --self-crossings ITEM: per request a header line with the number of crossings and the two index ranges, then
+    one line per crossing in the order of the edges."""
+    recs, offsets, infos = r.crossings([p[0] for p in pairs], [p[1] for p in pairs])
+    s_a, _ = r.crossing_positions(recs)
+    for k, ((a, b), info) in enumerate(zip(pairs, infos)):
+        what = f"self-crossings item {a}" if a == b else f"crossings items {a},{b}"
+        print(f"{what}: {int(info['n_crossings'])} edges {int(info['n_a'])} x {int(info['n_b'])}" + (" (too many pairs)" if int(info["flags"]) & 2 else ""))
+        for p in range(int(offsets[k]), int(offsets[k + 1])):
+            print(crossing_line(recs[p], s_a[p]))
+
+
 def bounds_record(r, words=None) -> dict:
     """--bounds: the box and the counts of the whole scene (words None) or of the items whose word is non-zero."""
     box, n_items, n_boxed = r.selection_bounds(words)
@@ -240,6 +262,8 @@ def main(argv=None) -> int:
     ap.add_argument("--resample-step", action="append", default=[], metavar="ITEM,STEP[,START]", help="resampling: the same for a point every STEP pixels along item ITEM from START pixels on (default 0), as many as fit; may be repeated")
     ap.add_argument("--trim", action="append", default=[], metavar="ITEM,START,END", help="trimming: print the piece of item ITEM between START and END pixels along it (END may be inf) -- a header line with the item's length in pixels and the piece's numbers of vertices and runs, then one line per vertex: 'move' starts a run, '(cut)' marks an interpolated end; may be repeated")
     ap.add_argument("--trim-parts", action="append", default=[], metavar="ITEM,M", help="trimming: the same for each of M even pieces of item ITEM, in order; may be repeated")
+    ap.add_argument("--crossings", action="append", default=[], metavar="A,B", help="item crossings: print every point where an edge of item A crosses an edge of item B -- a header line with the number of crossings and the two items' numbers of edge indices, then one line per crossing in the order of the edges: the point, the segment and the parameter on either item, how many pixels along A it lies, and which way B crosses A; may be repeated")
+    ap.add_argument("--self-crossings", action="append", default=[], metavar="ITEM", help="item crossings: the same for the points where item ITEM crosses itself, each once; may be repeated")
     args = ap.parse_args(argv)
     try:
         trim_ranges = [(int(p.split(",")[0]), float(p.split(",")[1]), float(p.split(",")[2])) for p in args.trim]
@@ -253,6 +277,18 @@ def main(argv=None) -> int:
             raise ValueError
     except (ValueError, IndexError):
         ap.error("--trim-parts takes ITEM,M with 1 <= M <= 1048576")
+    try:
+        crossing_pairs = [(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.crossings]
+        if any(p.count(",") != 1 for p in args.crossings) or any(not 0 <= i <= 0xFFFFFFFF for pair in crossing_pairs for i in pair):
+            raise ValueError
+    except (ValueError, IndexError):
+        ap.error("--crossings takes A,B")
+    try:
+        crossing_pairs += [(int(p), int(p)) for p in args.self_crossings]
+        if any(not 0 <= i <= 0xFFFFFFFF for i, _ in crossing_pairs):
+            raise ValueError
+    except ValueError:
+        ap.error("--self-crossings takes ITEM")
     try:
         resample_even =[(int(p.split(",")[0]), int(p.split(",")[1])) for p in args.resample]
         if any(len(p.split(",")) != 2 for p in args.resample) or any(i < 0 or i > 0xFFFFFFFF or not 0 <= n <= 1 << 20 for i, n in resample_even):
@@ -373,6 +409,8 @@ def main(argv=None) -> int:
             print_resampled(r, resample_even, resample_step)
         if trim_ranges or trim_parts:  # per piece a header line, then one line per vertex
             print_trimmed(r, trim_ranges, trim_parts)
+        if crossing_pairs:  # per request a header line, then one line per crossing
+            print_crossings(r, crossing_pairs)
         if args.coverage:  # one line per item that covers a pixel of the view
             print_coverage(r, args)
         if args.hidden:  # one line: the items no pixel of the view shows

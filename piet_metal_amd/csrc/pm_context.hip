@@ -49,6 +49,7 @@
 #include "pm_measure.h"    // pm_item_lengths_kernel, pm_points_at_length_kernel, pm_positions_on_edges_kernel: path measurement
 #include "pm_resample.h"   // pm_resample_kernel: many points along an item in one walk
 #include "pm_trim.h"       // pm_trim_kernel: the piece of an item between two lengths
+#include "pm_crossings.h"  // pm_crossings_kernel: every point where two items' edges cross
 #include "pm_layout.h"
 
 namespace {
@@ -3590,6 +3591,108 @@ int pm_trim_items(pm_ctx *c, const pm_trim_query *q, size_t n, uint32_t flags, p
     PM_TRY(hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < n; ++k) {
         const size_t wrote = std::min<size_t>(q[k].cap, info[k].n_vertices);
+        if (wrote != 0) std::memcpy(out + q[k].first, got.data() + q[k].first, wrote * sizeof(*out));
+    }
+    return PM_OK;
+}
+
+// ---- item crossings (pm_crossings.h; decision D29) ------------------------------------------------------------------------------------------
+namespace {
+static_assert(PM_CROSSINGS_TRUNCATED == pm::kCrossingsTruncated && PM_CROSSINGS_TOO_MANY == pm::kCrossingsTooMany && PM_CROSSINGS_MAX_PAIRS == pm::kCrossingsMaxPairs,
+              "pm_crossings.h's constants are the header's");
+static_assert(sizeof(pm_crossings_query) == 16 && offsetof(pm_crossings_query, item_a) == 0 && offsetof(pm_crossings_query, item_b) == 4 &&
+                  offsetof(pm_crossings_query, first) == 8 && offsetof(pm_crossings_query, cap) == 12,
+              "the request pm_crossings_kernel reads");
+static_assert(sizeof(pm_crossing) == 48 && offsetof(pm_crossing, item_a) == 0 && offsetof(pm_crossing, index_a) == 4 && offsetof(pm_crossing, t) == 8 &&
+                  offsetof(pm_crossing, item_b) == 16 && offsetof(pm_crossing, index_b) == 20 && offsetof(pm_crossing, u) == 24 && offsetof(pm_crossing, x) == 32 &&
+                  offsetof(pm_crossing, y) == 36 && offsetof(pm_crossing, side) == 40 && sizeof(pm_edge_query) == 16,
+              "the record pm_crossings_kernel writes: two pm_edge_query, the point, the side");
+static_assert(sizeof(pm_crossings_info) == 16 && offsetof(pm_crossings_info, n_crossings) == 0 && offsetof(pm_crossings_info, flags) == 4 &&
+                  offsetof(pm_crossings_info, n_a) == 8 && offsetof(pm_crossings_info, n_b) == 12,
+              "the info pm_crossings_kernel writes");
+
+// The launches for n requests in device memory, on q
+int CrossingsEnqueue(pm_ctx *c, const uint8_t *d_q, size_t n, uint32_t flags, uint8_t *d_out, size_t out_cap, uint8_t *d_info, hipStream_t q) {
+    int r = QueryOrderBefore(c, q);
+    if (r != PM_OK) return r;
+    pm::CrossingsParams p{};
+    p.V = QueryView(c, flags);
+    p.out = d_out;
+    p.out_cap = out_cap;
+    for (size_t at = 0; at < n; at += kHitLaunchMax) {
+        p.q = d_q + sizeof(pm_crossings_query) * at;
+        p.info = d_info + sizeof(pm_crossings_info) * at;
+        p.n = static_cast<uint32_t>(std::min(n - at, kHitLaunchMax));
+        pm::LaunchCrossings(p, static_cast<uint32_t>(c->n_cus), q);
+    }
+    return QueryOrderBehind(c, q);
+}
+}  // namespace
+
+int pm_item_crossings_device(pm_ctx *c, const void *dev_q, size_t n, uint32_t flags, void *dev_out, size_t out_cap, void *dev_info, void *hip_stream) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    const int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!dev_q || !dev_info || (!dev_out && out_cap != 0)) {
+        SetError("pm_item_crossings_device: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    if (((reinterpret_cast<uintptr_t>(dev_q) | reinterpret_cast<uintptr_t>(dev_out) | reinterpret_cast<uintptr_t>(dev_info)) & 7u) != 0) {
+        SetError("pm_item_crossings_device: a device pointer is not 8-byte aligned");
+        return PM_ERR_INVALID;
+    }
+    return CrossingsEnqueue(c, static_cast<const uint8_t *>(dev_q), n, flags, static_cast<uint8_t *>(dev_out), out_cap, static_cast<uint8_t *>(dev_info),
+                            QueryStream(c, hip_stream));
+}
+
+int pm_item_crossings(pm_ctx *c, const pm_crossings_query *q, size_t n, uint32_t flags, pm_crossing *out, size_t out_cap, pm_crossings_info *info) {
+    if (!c) return PM_ERR_INVALID;
+    PM_TRY(hipSetDevice(c->device));
+    int r = HitCheck(c, flags);
+    if (r != PM_OK || n == 0) return r;
+    if (!q || !info) {
+        SetError("pm_item_crossings: a NULL pointer with n != 0");
+        return PM_ERR_INVALID;
+    }
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        if (q[k].first != total) {   // (a total beyond 2^32 cannot be named by a `first`: refused here)
+            SetError("pm_item_crossings: a request's first is not the sum of the caps before it");
+            return PM_ERR_INVALID;
+        }
+        total += q[k].cap;
+    }
+    if (total != 0 && !out) {
+        SetError("pm_item_crossings: out is NULL with records to write");
+        return PM_ERR_INVALID;
+    }
+    if (total > out_cap || total > kMeasureBatch) return PM_ERR_CAPACITY;
+    // the staging buffer: {records, then per batch of requests: infos, requests}
+    const size_t batch = std::min(n, kMeasureBatch), at_info = total * sizeof(*out), at_q = at_info + batch * sizeof(*info);
+    PM_TRY(QueryStaging(c, at_q + batch * sizeof(*q)));
+    for (size_t at = 0; at < n; at += batch) {
+        const size_t m = std::min(batch, n - at);
+        PM_TRY(hipMemcpyAsync(c->d_stage + at_q, q + at, m * sizeof(*q), hipMemcpyHostToDevice, c->stream));
+        r = CrossingsEnqueue(c, c->d_stage + at_q, m, flags, c->d_stage, total, c->d_stage + at_info, c->stream);
+        if (r != PM_OK) return r;
+        PM_TRY(hipMemcpyAsync(info + at, c->d_stage + at_info, m * sizeof(*info), hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+    }
+    if (total == 0) return PM_OK;
+    // an answer shorter than its cap leaves rows of its range that the device did not write: those stay the caller's
+    bool exact = true;
+    for (size_t k = 0; k < n && exact; ++k) exact = info[k].n_crossings >= q[k].cap;
+    if (exact) {
+        PM_TRY(hipMemcpyAsync(out, c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+        PM_TRY(hipStreamSynchronize(c->stream));
+        return PM_OK;
+    }
+    std::vector<pm_crossing> got(total);
+    PM_TRY(hipMemcpyAsync(got.data(), c->d_stage, total * sizeof(*out), hipMemcpyDeviceToHost, c->stream));
+    PM_TRY(hipStreamSynchronize(c->stream));
+    for (size_t k = 0; k < n; ++k) {
+        const size_t wrote = std::min<size_t>(q[k].cap, info[k].n_crossings);
         if (wrote != 0) std::memcpy(out + q[k].first, got.data() + q[k].first, wrote * sizeof(*out));
     }
     return PM_OK;

@@ -1,5 +1,5 @@
 // What the query kernels share: pm_hit_test.h, pm_hit_frame.h, pm_hit_rect.h, pm_hit_poly.h, pm_hit_stack.h, pm_coverage.h, pm_snap.h, pm_snap_cross.h,
-// pm_bounds.h, pm_measure.h, pm_resample.h and pm_trim.h.  None of them is on the frame path: they read the scene and the scene index (pm_index_kernel), nothing a frame
+// pm_bounds.h, pm_measure.h, pm_resample.h, pm_trim.h and pm_crossings.h.  None of them is on the frame path: they read the scene and the scene index (pm_index_kernel), nothing a frame
 // writes.  Included by pm_context.hip through those headers, in whose unit the kernels are compiled.
 //
 //  * SceneView: what a kernel reads of the context, the first member of every query's params (the host fills it in ONE place,

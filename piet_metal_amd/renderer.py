@@ -54,6 +54,12 @@ TRIM_QUERY_DTYPE = np.dtype([("item", "<u4"), ("mode", "<u4"), ("first", "<u4"),
 TRIM_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("index", "<u4"), ("flags", "<u4")])
 TRIM_INFO_DTYPE = np.dtype([("length", "<u8"), ("n_vertices", "<u4"), ("n_runs", "<u4"), ("kind", "<u4"), ("flags", "<u4")])
 assert (TRIM_QUERY_DTYPE.itemsize, TRIM_VERTEX_DTYPE.itemsize, TRIM_INFO_DTYPE.itemsize) == (32, 16, 24)
+# the requests, records and infos of item crossings (decision D29); a record's first and second 16 bytes are each an EDGE_QUERY_DTYPE
+CROSSINGS_QUERY_DTYPE = np.dtype([("item_a", "<u4"), ("item_b", "<u4"), ("first", "<u4"), ("cap", "<u4")])
+CROSSING_DTYPE = np.dtype([("item_a", "<u4"), ("index_a", "<u4"), ("t", "<f4"), ("reserved_a", "<u4"), ("item_b", "<u4"), ("index_b", "<u4"), ("u", "<f4"),
+                           ("reserved_b", "<u4"), ("x", "<f4"), ("y", "<f4"), ("side", "<u4"), ("reserved", "<u4")])
+CROSSINGS_INFO_DTYPE = np.dtype([("n_crossings", "<u4"), ("flags", "<u4"), ("n_a", "<u4"), ("n_b", "<u4")])
+assert (CROSSINGS_QUERY_DTYPE.itemsize, CROSSING_DTYPE.itemsize, CROSSINGS_INFO_DTYPE.itemsize) == (16, 48, 16)
 
 
 def length_units(px) -> int:
@@ -1138,6 +1144,76 @@ class Renderer:
         if stream is not None and not s:  # (torch's default stream: see render_to)
             _warn_default_stream()
             self.sync()
+
+    # ---- item crossings (decision D29) -------------------------------------------------------
+    def crossings(self, items_a, items_b, skip_transparent: bool = False):
+        """Every point where an edge of items_a[k] crosses an edge of items_b[k] (one item each, or one per request; the same item
+        twice asks for its self-crossings, each once).  Returns (records, offsets, infos): the packed CROSSING_DTYPE records --
+        request k's are records[offsets[k]:offsets[k + 1]], in the order (index_a, index_b) --, and per request a
+        CROSSINGS_INFO_DTYPE record {n_crossings, flags, n_a, n_b}.  A request of more than PM_CROSSINGS_MAX_PAIRS index pairs has
+        the flag PM_CROSSINGS_TOO_MANY and no records: split the item with trim.  Two calls: the count pass, then exactly packed."""
+        a, b = np.asarray(items_a, dtype=np.uint32), np.asarray(items_b, dtype=np.uint32)
+        if a.ndim > 1 or b.ndim > 1 or (a.ndim == 1 and b.ndim == 1 and len(a) != len(b)):
+            raise ValueError("one item, or one per request, on either side")
+        n = len(a) if a.ndim == 1 else (len(b) if b.ndim == 1 else 1)
+        q = np.zeros(n, CROSSINGS_QUERY_DTYPE)
+        q["item_a"] = a
+        q["item_b"] = b
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        info = np.zeros(n, CROSSINGS_INFO_DTYPE)
+        _lib.check(self._lib.pm_item_crossings(self._h, q.ctypes.data, n, flags, None, 0, info.ctypes.data), "pm_item_crossings")
+        offsets = np.zeros(n + 1, np.int64)
+        np.cumsum(info["n_crossings"], out=offsets[1:])
+        if offsets[-1] > 1 << 20:
+            raise ValueError(f"a crossings call answers at most {1 << 20} records")
+        q["first"] = offsets[:-1]
+        q["cap"] = info["n_crossings"]
+        out = np.zeros(int(offsets[-1]), CROSSING_DTYPE)
+        if len(out):
+            _lib.check(self._lib.pm_item_crossings(self._h, q.ctypes.data, n, flags, out.ctypes.data, len(out), info.ctypes.data), "pm_item_crossings")
+        return out, offsets, info
+
+    def self_crossings(self, items, skip_transparent: bool = False):
+        """crossings(items, items): where every item of `items` crosses itself."""
+        it = np.asarray(items, dtype=np.uint32)
+        return self.crossings(it, it, skip_transparent)
+
+    def crossings_tensor(self, requests, out, info, stream=None, skip_transparent: bool = False) -> None:
+        """Crossings on torch CUDA tensors, asynchronous: requests int32 [n, 4] (the 16-byte CROSSINGS_QUERY_DTYPE records), out int32
+        [cap, 12] (CROSSING_DTYPE records), info int32 [n, 4] (CROSSINGS_INFO_DTYPE), all contiguous.  A request's `first` and `cap`
+        are the caller's: record p goes to out[first + p] for p < cap, and no row at or beyond the tensor's end is written.  `stream`
+        as in hit_test_tensor."""
+        if not (requests.is_cuda and out.is_cuda and info.is_cuda) or str(requests.dtype) != "torch.int32" or requests.dim() != 2 or requests.shape[1] != 4 or \
+                not requests.is_contiguous():
+            raise TypeError("crossings_tensor needs a contiguous CUDA int32 tensor [n, 4]")
+        n = requests.shape[0]
+        if str(out.dtype) != "torch.int32" or out.dim() != 2 or out.shape[1] != 12 or not out.is_contiguous():
+            raise TypeError("crossings_tensor writes a contiguous CUDA int32 tensor [cap, 12]")
+        if str(info.dtype) != "torch.int32" or tuple(info.shape) != (n, 4) or not info.is_contiguous():
+            raise TypeError("crossings_tensor writes a contiguous CUDA int32 tensor [n, 4] of infos")
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        s = stream.cuda_stream if stream is not None else None
+        _lib.check(self._lib.pm_item_crossings_device(self._h, requests.data_ptr(), n, flags, out.data_ptr(), out.shape[0], info.data_ptr(), s),
+                   "pm_item_crossings_device")
+        if stream is not None and not s:  # (torch's default stream: see render_to)
+            _warn_default_stream()
+            self.sync()
+
+    def crossing_positions(self, records, skip_transparent: bool = False):
+        """(s_a, s_b): how far along item A and along item B every crossing of `records` (CROSSING_DTYPE) lies, in units of 2^-16 px
+        as uint64 arrays -- the record's two 16-byte halves through positions_on_edges, which answers PM_MEASURE_FOUND for every
+        one.  On the device the same is `rec.view(-1, 3, 4)[:, :2].reshape(-1, 4)` of a crossings_tensor `out`, made contiguous,
+        into positions_on_edges_tensor: rows 2 k and 2 k + 1 are crossing k's positions along A and along B."""
+        rec = np.ascontiguousarray(records, dtype=CROSSING_DTYPE)
+        if rec.ndim != 1:
+            raise ValueError("records is a 1-D array of CROSSING_DTYPE")
+        q = np.ascontiguousarray(rec.view(np.uint32).reshape(-1, 3, 4)[:, :2]).reshape(-1).view(EDGE_QUERY_DTYPE)
+        out = np.zeros(len(q), LENGTH_AT_DTYPE)
+        flags = _lib.PM_HIT_SKIP_TRANSPARENT if skip_transparent else 0
+        _lib.check(self._lib.pm_positions_on_edges(self._h, q.ctypes.data, len(q), flags, out.ctypes.data), "pm_positions_on_edges")
+        if len(out) and not np.all(out["status"] == _lib.PM_MEASURE_FOUND):
+            raise ValueError("a record names no edge of the resident scene")
+        return out["s"][0::2].copy(), out["s"][1::2].copy()
 
     def path_lengths(self, skip_transparent: bool = False):
         """(lengths, n_items) per path of the PathSet: the sum of item_lengths over the items each path produced (item_paths), in
